@@ -16,7 +16,11 @@ md_bench_run (C); Python only brackets it.
 
 `python bench.py --gpus N` starts its N ranks itself when it was not started by torch.distributed.run (WORLD_SIZE unset).
 
-Also on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes, after the timed steps, the sites the last step computed (see dump_outputs).
+Everything below is measured only with --full.
+
+Also on the JSON line (--full):
   roofline     -- the kernel family that takes the most device time per chunk, and under "kernels" every family: algorithmic bytes
                   per launch / HIP-event time per launch while rotating over the R intervals on one stream, vs 8 TB/s
   cpu_baseline -- the CPU oracle (`oracle/`, "port") end to end on a 32 Mb sample of the same workload with all host cores and
@@ -26,6 +30,7 @@ Also on the JSON line:
   streamed     -- the resident loop's chunks with H2D upload + kernels + D2H of the sites per chunk (registered staging, two slots)
 """
 import argparse
+import atexit
 import shutil
 import ctypes as C
 import json
@@ -72,6 +77,43 @@ def median_run(fn, runs=3):
     for _ in range(runs):
         t1 = time.perf_counter(); fn(); ts.append(time.perf_counter() - t1)
     return statistics.median(ts), ts
+
+
+DUMP_CAP_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, dev, slots):
+    """--dump-outputs: what a caller of the timed path receives, per resident interval (slot order), after the last step -- the md_sites
+    of md_dev_download: site records (pos, nmeth, nunmeth, meta) in the order given, and the variant evidence (noff, nvar) when the
+    options ask for it.  Written as float64 (the uint32 values exactly): sites.npy [n, 4], site_var.npy [n, 2], n_sites.npy [R] (the
+    sites of each interval).  Beyond DUMP_CAP_BYTES a fixed seeded sample of the rows is written, their indices in sample_rows.npy.
+    Each interval is launched once more on its own here; md_bench_verify (run by the caller for every group) has compared those site
+    records byte for byte with what the timed loop left in its send buffer.  It does not compare the variant evidence: site_var is what
+    the single-chunk launch gives, not shown to equal the loop's."""
+    sites, var, counts = [], [], []
+    for i in slots:
+        dev.launch(i)
+        s = dev.download(i)
+        n = int(s.n_sites)
+        counts.append(n)
+        if n:
+            sites.append(np.ctypeslib.as_array(C.cast(s.site, C.POINTER(C.c_uint32)), shape=(n, 4)).astype(np.float64))
+            if s.var:
+                var.append(np.ctypeslib.as_array(C.cast(s.var, C.POINTER(C.c_uint32)), shape=(n, 2)).astype(np.float64))
+    out = {"sites": np.concatenate(sites) if sites else np.zeros((0, 4))}
+    if var:
+        out["site_var"] = np.concatenate(var)
+    rows, row_bytes = out["sites"].shape[0], sum(8 * a.shape[1] for a in out.values())
+    if rows * row_bytes + 8 * len(slots) > DUMP_CAP_BYTES:
+        keep = (DUMP_CAP_BYTES - 8 * len(slots)) // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(S1_SEED).choice(rows, size=keep, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["sample_rows"] = idx.astype(np.float64)
+    out["n_sites"] = np.asarray(counts, dtype=np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, a in out.items():
+        np.save(out_dir / f"{k}.npy", a)
+    log(f"[bench] outputs of the last step: {rows} sites of {len(slots)} intervals -> {out_dir}")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -412,7 +454,12 @@ def main():
     ap.add_argument("--no-exchange", action="store_true", help="N ranks without the gather of site buffers to rank 0 (what the run falls back to when no communicator can be made)")
     ap.add_argument("--devices", default="", help="comma list: physical device of each local rank (tests: two ranks on one GPU)")
     ap.add_argument("--data-dir", default="", help="keep the synthetic inputs here and reuse them on the next run (profiling passes)")
+    ap.add_argument("--full", action="store_true", help="also the kernel rooflines, the streamed and dense-context legs, the verification of the timed loop's "
+                                                        "results and the CPU baseline / end-to-end legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the sites of the last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)
@@ -445,6 +492,7 @@ def main():
 
     R = max(2 * GROUP, (args.resident + GROUP - 1) // GROUP * GROUP)
     work = Path(tempfile.mkdtemp(prefix=f"mdk_bench_r{rank}_"))
+    atexit.register(shutil.rmtree, work, ignore_errors=True)          # (the synthetic inputs too, unless --data-dir keeps them; on an error as well)
     data = Path(args.data_dir) if args.data_dir else work
     data.mkdir(parents=True, exist_ok=True)
     prefix = data / f"S1_r{rank}_{R}x{args.length}_{args.coverage}"
@@ -482,7 +530,7 @@ def main():
             a = np.ctypeslib.as_array(C.cast(sites.site, C.POINTER(C.c_uint32)), shape=(int(sites.n_sites), 4))      # md_site = {pos, nmeth, nunmeth, meta}
             c = a[:, 1].astype(np.int64) + a[:, 2]
             all_calls += int(c.sum()); cpg_calls += int(c[((a[:, 3] >> 1) & 3) == 0].sum())
-        if n_chunks < 2:
+        if args.full and n_chunks < 2:
             b = chunk.raw
             cat = b"".join(C.string_at(b.range[i].ptr, b.range[i].bytes) for i in range(b.n_ranges))
             offs = np.asarray(mdk.raw_record_offsets(b), dtype=np.uint32).tobytes()
@@ -571,12 +619,22 @@ def main():
     run(args.steps)
     fence()
     dt = time.perf_counter() - t0
-    if args.steps:
-        rc = L.md_bench_verify(bench)
-        assert rc == 0, L.md_dev_last_error()
     exchanges, bytes_per_exchange = int(res.exchanges), int(res.bytes_per_exchange)
     log(f"[bench] rank {rank}: timed loop {dt:.2f} s")
+    if args.steps and (args.full or args.dump_outputs or world > 1):      # (N ranks: also that every peer's results reached rank 0)
+        rc = L.md_bench_verify(bench)
+        assert rc == 0, L.md_dev_last_error()
+    if args.dump_outputs:
+        # the last step presents every resident interval; the loop's last launch (verified above) holds the last group of them.  Every other
+        # group is run once more through the same loop and verified the same way, so that the sites written below -- md_dev_download of each
+        # interval -- are, group by group, what the timed path computed
+        r_extra = mdk.md_bench_run_result()
+        for j in range(R // GROUP - 1):
+            assert L.md_bench_run(bench, j + 1, C.byref(r_extra)) == 0, L.md_dev_last_error()
+            assert L.md_bench_verify(bench) == 0, L.md_dev_last_error()
     L.md_bench_close(bench)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), dev, slots)
 
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64)
@@ -588,139 +646,142 @@ def main():
     else:
         total_cpg_calls, total_calls, total_sites = cpg_calls, all_calls, int(n_sites_sum)
 
-    # kernel-level timing with HIP events on the launch stream, inside the library, rotating over the R resident intervals
-    br = dev.bench_rotate(slots, 8, 200, per_launch=GROUP)
-    br_single = dev.bench_rotate(slots, 2 * R, max(200, 50 * R))
-    prep_ms = C.c_float(0); prep1_ms = C.c_float(0)
-    assert L.md_dev_bench_prep_rotate(dev.h, slot_arr, R, GROUP, 2 * (R // GROUP), 40 * (R // GROUP), C.byref(prep_ms)) == 0, L.md_dev_last_error()
-    assert L.md_dev_bench_prep_rotate(dev.h, slot_arr, R, 1, R, 10 * R, C.byref(prep1_ms)) == 0, L.md_dev_last_error()
-    pile_s, prep_s = br.ms_pileup / 1e3, prep_ms.value / 1e3
-    # algorithmic bytes per LAUNCH (GROUP chunks).  Pileup: SURVEY.md 8d (reads' payload + reference + sites).  Preparation: its input -- every
-    # byte of the chunk's records, once -- + the 32-byte segments it writes; its intermediates (48 B per record, the name table) are overhead,
-    # not algorithmic bytes.  The numerator is the one rounds 3-5 used, so the fractions compare; since round 6 the scan fetches
-    # only the lines its fields lie in (1.7 of a record's 2.2: `traffic` below is what the counters saw), and `step` prices preparation +
-    # pileup with SURVEY.md 8d's own per-chunk figure.
-    pile_bytes = int(br.algo_bytes)
-    prep_bytes = int((raw_bytes / R + 32.0 * segs / R) * GROUP)
-    fam = {
-        "pileup": {"kernel": "k_pileup_multi<false,false>", "bound": "hbm", "kernel_ms": br.ms_pileup, "kernel_ms_per_chunk": br.ms_pileup / GROUP, "algo_bytes_per_launch": pile_bytes,
-                   "achieved": pile_bytes / pile_s / 1e9 if pile_s > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s"},
-        "preparation": {"kernel": "k_prep_zero + k_prep_scan + k_prep_segs", "bound": "hbm", "kernel_ms": prep_ms.value, "kernel_ms_per_chunk": prep_ms.value / GROUP, "algo_bytes_per_launch": prep_bytes,
-                        "achieved": prep_bytes / prep_s / 1e9 if prep_s > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "one_chunk_per_launch_ms": prep1_ms.value},
-    }
-    for f in fam.values():
-        f["frac"] = f["achieved"] / HBM_PEAK_GBS
-    dominant = max(fam, key=lambda k: fam[k]["kernel_ms"])
-    step_bytes = pile_bytes           # SURVEY.md 8d's per-unit figure is the pileup's: the step moves it once per chunk
-    step_s = pile_s + prep_s
-    br1 = dev.bench(0, 5, 200)                 # one interval relaunched on cache-resident data, for comparison with round 1
+    # --full: the kernel rooflines, the streamed and dense-context legs, the HBM traffic of the dominant family
+    br = fam = dominant = streamed = dense = None
+    if args.full:
+        # kernel-level timing with HIP events on the launch stream, inside the library, rotating over the R resident intervals
+        br = dev.bench_rotate(slots, 8, 200, per_launch=GROUP)
+        br_single = dev.bench_rotate(slots, 2 * R, max(200, 50 * R))
+        prep_ms = C.c_float(0); prep1_ms = C.c_float(0)
+        assert L.md_dev_bench_prep_rotate(dev.h, slot_arr, R, GROUP, 2 * (R // GROUP), 40 * (R // GROUP), C.byref(prep_ms)) == 0, L.md_dev_last_error()
+        assert L.md_dev_bench_prep_rotate(dev.h, slot_arr, R, 1, R, 10 * R, C.byref(prep1_ms)) == 0, L.md_dev_last_error()
+        pile_s, prep_s = br.ms_pileup / 1e3, prep_ms.value / 1e3
+        # algorithmic bytes per LAUNCH (GROUP chunks).  Pileup: SURVEY.md 8d (reads' payload + reference + sites).  Preparation: its input -- every
+        # byte of the chunk's records, once -- + the 32-byte segments it writes; its intermediates (48 B per record, the name table) are overhead,
+        # not algorithmic bytes.  The numerator is the one rounds 3-5 used, so the fractions compare; since round 6 the scan fetches
+        # only the lines its fields lie in (1.7 of a record's 2.2: `traffic` below is what the counters saw), and `step` prices preparation +
+        # pileup with SURVEY.md 8d's own per-chunk figure.
+        pile_bytes = int(br.algo_bytes)
+        prep_bytes = int((raw_bytes / R + 32.0 * segs / R) * GROUP)
+        fam = {
+            "pileup": {"kernel": "k_pileup_multi<false,false>", "bound": "hbm", "kernel_ms": br.ms_pileup, "kernel_ms_per_chunk": br.ms_pileup / GROUP, "algo_bytes_per_launch": pile_bytes,
+                       "achieved": pile_bytes / pile_s / 1e9 if pile_s > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s"},
+            "preparation": {"kernel": "k_prep_zero + k_prep_scan + k_prep_segs", "bound": "hbm", "kernel_ms": prep_ms.value, "kernel_ms_per_chunk": prep_ms.value / GROUP, "algo_bytes_per_launch": prep_bytes,
+                            "achieved": prep_bytes / prep_s / 1e9 if prep_s > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "one_chunk_per_launch_ms": prep1_ms.value},
+        }
+        for f in fam.values():
+            f["frac"] = f["achieved"] / HBM_PEAK_GBS
+        dominant = max(fam, key=lambda k: fam[k]["kernel_ms"])
+        step_bytes = pile_bytes           # SURVEY.md 8d's per-unit figure is the pileup's: the step moves it once per chunk
+        step_s = pile_s + prep_s
+        br1 = dev.bench(0, 5, 200)                 # one interval relaunched on cache-resident data, for comparison with round 1
 
-    # streamed: the same chunk with its H2D upload (registered staging) and the D2H of its sites, two slots, chunk k+1 uploaded
-    # and launched while chunk k is downloaded
-    streamed = None
-    if world == 1 and len(keep_batches) == 2:
-        pinned, batches, keep = [], [], []
-        L.md_host_alloc.restype = C.c_void_p
-        for (tid, beg, end, n_rec, woff, wlen, cat, offs) in keep_batches:
-            pc = L.md_host_alloc(C.c_uint64(len(cat))); po = L.md_host_alloc(C.c_uint64(max(len(offs), 8 << 20)))
-            C.memmove(pc, cat, len(cat)); C.memmove(po, offs, len(offs))
-            pinned += [pc, po]
-            rg = (mdk.md_raw_range * 1)(); rg[0].ptr = C.cast(pc, C.POINTER(C.c_uint8)); rg[0].bytes = len(cat)
-            b = mdk.md_raw_batch(); b.tid = tid; b.beg = beg; b.end = end; b.n_ranges = 1; b.range = rg; b.n_records = n_rec
-            b.rec_off = C.cast(po, C.POINTER(C.c_uint32)); b.woff = woff; b.wlen = wlen
-            batches.append(b); keep.append(rg)
-        n_stream = 200
-        for timed in (False, True):
-            nn = n_stream if timed else 10
-            ts = time.perf_counter()
-            dev.submit_raw(R, batches[0])
-            for k in range(1, nn):
-                dev.submit_raw(R + (k & 1), batches[k & 1])
-                dev.download(R + ((k - 1) & 1))
-            dev.download(R + ((nn - 1) & 1))
-            t_stream = time.perf_counter() - ts
-        h2d = (len(keep_batches[0][6]) + len(keep_batches[0][7]) + len(keep_batches[1][6]) + len(keep_batches[1][7])) / 2
-        per_chunk_calls = cpg_calls / R
-        streamed = {"ms_per_chunk": t_stream / n_stream * 1e3, "value": per_chunk_calls * n_stream / t_stream, "unit": "CpG calls/s", "h2d_bytes_per_chunk": int(h2d),
-                    "h2d_GBps": h2d * n_stream / t_stream / 1e9,
-                    "note": "per chunk: hipMemcpyAsync of the chunk's BAM records + record table from registered huge-page staging memory, the preparation kernels, k_pileup, "
-                            "D2H of the site records; two slots (chunk k+1 is uploaded and launched while chunk k is downloaded), one chunk per launch"}
-        for p in pinned:
-            L.md_host_free(C.c_void_p(p))
+        # streamed: the same chunk with its H2D upload (registered staging) and the D2H of its sites, two slots, chunk k+1 uploaded
+        # and launched while chunk k is downloaded
+        streamed = None
+        if world == 1 and len(keep_batches) == 2:
+            pinned, batches, keep = [], [], []
+            L.md_host_alloc.restype = C.c_void_p
+            for (tid, beg, end, n_rec, woff, wlen, cat, offs) in keep_batches:
+                pc = L.md_host_alloc(C.c_uint64(len(cat))); po = L.md_host_alloc(C.c_uint64(max(len(offs), 8 << 20)))
+                C.memmove(pc, cat, len(cat)); C.memmove(po, offs, len(offs))
+                pinned += [pc, po]
+                rg = (mdk.md_raw_range * 1)(); rg[0].ptr = C.cast(pc, C.POINTER(C.c_uint8)); rg[0].bytes = len(cat)
+                b = mdk.md_raw_batch(); b.tid = tid; b.beg = beg; b.end = end; b.n_ranges = 1; b.range = rg; b.n_records = n_rec
+                b.rec_off = C.cast(po, C.POINTER(C.c_uint32)); b.woff = woff; b.wlen = wlen
+                batches.append(b); keep.append(rg)
+            n_stream = 200
+            for timed in (False, True):
+                nn = n_stream if timed else 10
+                ts = time.perf_counter()
+                dev.submit_raw(R, batches[0])
+                for k in range(1, nn):
+                    dev.submit_raw(R + (k & 1), batches[k & 1])
+                    dev.download(R + ((k - 1) & 1))
+                dev.download(R + ((nn - 1) & 1))
+                t_stream = time.perf_counter() - ts
+            h2d = (len(keep_batches[0][6]) + len(keep_batches[0][7]) + len(keep_batches[1][6]) + len(keep_batches[1][7])) / 2
+            per_chunk_calls = cpg_calls / R
+            streamed = {"ms_per_chunk": t_stream / n_stream * 1e3, "value": per_chunk_calls * n_stream / t_stream, "unit": "CpG calls/s", "h2d_bytes_per_chunk": int(h2d),
+                        "h2d_GBps": h2d * n_stream / t_stream / 1e9,
+                        "note": "per chunk: hipMemcpyAsync of the chunk's BAM records + record table from registered huge-page staging memory, the preparation kernels, k_pileup, "
+                                "D2H of the site records; two slots (chunk k+1 is uploaded and launched while chunk k is downloaded), one chunk per launch"}
+            for p in pinned:
+                L.md_host_free(C.c_void_p(p))
 
-    # the dense-context configuration (BASELINE.json configs[2]: --CHG --CHH with --OT/--OB trimming on the same reads) through its own
-    # kernel (8 lanes of a wavefront per segment), same resident intervals, same rotation, same 8-chunk launches
-    dense = None
-    if world == 1 and not extra and not args.synth_args and args.length == 1_000_000:
-        plan2 = mdk.Plan([str(prefix) + ".fa", str(prefix) + ".bam", "--chunkSize", str(args.length), "-@", str(min(32, os.cpu_count() or 1)), "--CHG", "--CHH",
-                          "--OT", "6,146,6,146", "--OB", "6,146,6,146", "-o", str(work / "dense")])
-        plan2.set_prep(1)
-        cfg2 = plan2.dev_cfg(); cfg2.n_slots = R
-        dev2 = mdk.Device(cfg2, device=dev_index); dev2.set_prep(plan2.prep_cfg())
-        calls2 = 0
-        for i in range(R):
-            c2 = plan2.next_chunk(); plan2.ensure_reference(dev2, c2.tid); dev2.upload_raw(i, c2.raw); dev2.launch(i)
-            st2 = dev2.download(i)
-            if st2.n_sites:
-                a2 = np.ctypeslib.as_array(C.cast(st2.site, C.POINTER(C.c_uint32)), shape=(int(st2.n_sites), 4))
-                calls2 += int(a2[:, 1].sum(dtype=np.int64) + a2[:, 2].sum(dtype=np.int64))
-        brd = dev2.bench_rotate(slots, 8, 100, per_launch=GROUP)
-        dense = {"workload": "the same R resident intervals with --CHG --CHH --OT 6,146,6,146 --OB 6,146,6,146 (BASELINE.json configs[2])", "kernel": "k_pileup_multi<false,true> (8 lanes per segment)",
-                 "tile": int(brd.tile), "kernel_ms": brd.ms_pileup, "kernel_ms_per_chunk": brd.ms_pileup / GROUP, "algo_bytes_per_launch": int(brd.algo_bytes),
-                 "achieved": brd.algo_bytes / (brd.ms_pileup / 1e3) / 1e9 if brd.ms_pileup > 0 else 0.0, "unit": "GB/s",
-                 "frac": brd.algo_bytes / (brd.ms_pileup / 1e3) / 1e9 / HBM_PEAK_GBS if brd.ms_pileup > 0 else 0.0,
-                 "sites_per_interval": int(brd.n_sites) // GROUP, "calls_per_interval": calls2 // R,
-                 "value": (calls2 / R) * GROUP / (brd.ms_pileup / 1e3) if brd.ms_pileup > 0 else 0.0, "value_unit": "cytosine calls/s (all contexts), pileup kernel only"}
-        dev2.close(); plan2.close()
+        # the dense-context configuration (BASELINE.json configs[2]: --CHG --CHH with --OT/--OB trimming on the same reads) through its own
+        # kernel (8 lanes of a wavefront per segment), same resident intervals, same rotation, same 8-chunk launches
+        dense = None
+        if world == 1 and not extra and not args.synth_args and args.length == 1_000_000:
+            plan2 = mdk.Plan([str(prefix) + ".fa", str(prefix) + ".bam", "--chunkSize", str(args.length), "-@", str(min(32, os.cpu_count() or 1)), "--CHG", "--CHH",
+                              "--OT", "6,146,6,146", "--OB", "6,146,6,146", "-o", str(work / "dense")])
+            plan2.set_prep(1)
+            cfg2 = plan2.dev_cfg(); cfg2.n_slots = R
+            dev2 = mdk.Device(cfg2, device=dev_index); dev2.set_prep(plan2.prep_cfg())
+            calls2 = 0
+            for i in range(R):
+                c2 = plan2.next_chunk(); plan2.ensure_reference(dev2, c2.tid); dev2.upload_raw(i, c2.raw); dev2.launch(i)
+                st2 = dev2.download(i)
+                if st2.n_sites:
+                    a2 = np.ctypeslib.as_array(C.cast(st2.site, C.POINTER(C.c_uint32)), shape=(int(st2.n_sites), 4))
+                    calls2 += int(a2[:, 1].sum(dtype=np.int64) + a2[:, 2].sum(dtype=np.int64))
+            brd = dev2.bench_rotate(slots, 8, 100, per_launch=GROUP)
+            dense = {"workload": "the same R resident intervals with --CHG --CHH --OT 6,146,6,146 --OB 6,146,6,146 (BASELINE.json configs[2])", "kernel": "k_pileup_multi<false,true> (8 lanes per segment)",
+                     "tile": int(brd.tile), "kernel_ms": brd.ms_pileup, "kernel_ms_per_chunk": brd.ms_pileup / GROUP, "algo_bytes_per_launch": int(brd.algo_bytes),
+                     "achieved": brd.algo_bytes / (brd.ms_pileup / 1e3) / 1e9 if brd.ms_pileup > 0 else 0.0, "unit": "GB/s",
+                     "frac": brd.algo_bytes / (brd.ms_pileup / 1e3) / 1e9 / HBM_PEAK_GBS if brd.ms_pileup > 0 else 0.0,
+                     "sites_per_interval": int(brd.n_sites) // GROUP, "calls_per_interval": calls2 // R,
+                     "value": (calls2 / R) * GROUP / (brd.ms_pileup / 1e3) if brd.ms_pileup > 0 else 0.0, "value_unit": "cytosine calls/s (all contexts), pileup kernel only"}
+            dev2.close(); plan2.close()
 
-    # HBM traffic of the dominant family, per launch: measured for THIS line when rocprofv3 is on the box -- one pass per counter (FETCH_SIZE,
-    # WRITE_SIZE: MI355X_MICROARCH.md's recipe) over tools/prep_bench.py, which launches the same kernels on the same 16 resident intervals, 8
-    # chunks per launch; only the dispatches with each kernel's largest grid (the 8-chunk launches) are averaged.  Without rocprofv3 the
-    # committed summary of a separate profiled run stands in, and the line says which.
-    traffic, traffic_info = None, None
-    fam_kernels = {"preparation": ["k_prep_zero", "k_prep_scan", "k_prep_segs"], "pileup": ["k_pileup_multi<false,false>"]}
-    under_profiler = any(os.environ.get(k) for k in ("HSA_TOOLS_LIB", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD", "ROCPROF_OUTPUT_PATH"))      # (this run is itself being profiled: no profiler inside a profiler)
-    if rank == 0 and world == 1 and not args.no_live_traffic and not under_profiler and not extra and not args.synth_args and args.length == 1_000_000 and shutil.which("rocprofv3"):
-        try:
-            import csv, glob
-            per = {}
-            for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
-                pd = work / f"pmc_{ctr}"
-                subprocess.run([shutil.which("rocprofv3"), "--kernel-trace", "--output-format", "csv", "--pmc", ctr, "-d", str(pd), "-o", "p", "--", sys.executable, str(REPO / "tools/prep_bench.py"), str(R)],
-                               cwd="/tmp", env=dict(os.environ, PREP_BENCH_FAST="2", TMPDIR="/tmp"), capture_output=True, text=True, timeout=400)
-                rows = {}
-                for f in glob.glob(f"{pd}/**/*counter_collection.csv", recursive=True):
-                    for r in csv.DictReader(open(f)):
-                        if r["Counter_Name"] != ctr:
-                            continue
-                        k = re.sub(r"\(.*\)\s*$", "", re.sub(r"^void\s+", "", r["Kernel_Name"].strip())).replace(", ", ",").replace(" ", "")
-                        rows.setdefault(k, []).append((int(r["Grid_Size"]), float(r["Counter_Value"])))
-                for k, v in rows.items():
-                    gmax = max(g for g, _ in v); big = [x for g, x in v if g >= 0.98 * gmax]
-                    per.setdefault(k, {})[ctr] = (sum(big) / len(big) * 1024.0, len(big))              # rocprofv3 reports KiB
-            ks = fam_kernels[dominant]
-            if all(k in per and "FETCH_SIZE" in per[k] and "WRITE_SIZE" in per[k] for k in ks):
-                fr = sum(per[k]["FETCH_SIZE"][0] for k in ks); wr = sum(per[k]["WRITE_SIZE"][0] for k in ks)
-                traffic = 2 * fr + wr
-                traffic_info = {"measured": "live: rocprofv3 --pmc passes run by this bench.py invocation (tools/prep_bench.py: the same kernels on the same resident intervals, 8 chunks per launch)",
-                                "kernels": ks, "dispatches": {k: per[k]["FETCH_SIZE"][1] for k in ks}, "fetch_raw_counter_bytes": fr, "write_raw_counter_bytes": wr,
-                                "per_kernel": {k: {"fetch_x2_plus_write": 2 * per[k]["FETCH_SIZE"][0] + per[k]["WRITE_SIZE"][0]} for k in ks},
-                                "note": "per launch, summed over the family's kernels: FETCH_SIZE x 2 (MI355X_MICROARCH.md: gfx950 tallies 128-byte requests as 64) + WRITE_SIZE"}
-        except Exception as ex:
-            log(f"[bench] live traffic counters failed: {ex!r}")
-    if traffic is None:
-        try:
-            # the round's final summary (rNNfin_*) if there is one, else the last one of the latest round by name
-            cand = sorted((REPO / "profiles").glob("r[0-9][0-9]*_rocprofv3_pmc_summary.json"), key=lambda q: (q.name[:3], "fin" in q.name.split("_")[0], q.name))
-            prof = json.load(open(cand[-1]))
-            k = prof["families"].get(dominant)
-            if k and not extra and not args.synth_args and args.length == 1_000_000 and k.get("chunks_per_launch") == GROUP:
-                traffic = k["hbm_bytes_per_launch"]["fetch_x2_plus_write"]
-                traffic_info = {"measured": "NOT this run: the committed summary of a separate profiled run", "file": cand[-1].name, "kernels": k["kernels"], "dispatches": k["dispatches"], "fetch_raw_counter_bytes": k["hbm_bytes_per_launch"]["fetch_raw"], "write_raw_counter_bytes": k["hbm_bytes_per_launch"]["write_raw"],
-                                "note": "per launch, summed over the family's kernels: FETCH_SIZE x 2 (MI355X_MICROARCH.md: gfx950 tallies 128-byte requests as 64) + WRITE_SIZE"}
-        except Exception:
-            pass
+        # HBM traffic of the dominant family, per launch: measured for THIS line when rocprofv3 is on the box -- one pass per counter (FETCH_SIZE,
+        # WRITE_SIZE) over tools/prep_bench.py, which launches the same kernels on the same 16 resident intervals, 8
+        # chunks per launch; only the dispatches with each kernel's largest grid (the 8-chunk launches) are averaged.  Without rocprofv3 the
+        # committed summary of a separate profiled run stands in, and the line says which.
+        traffic, traffic_info = None, None
+        fam_kernels = {"preparation": ["k_prep_zero", "k_prep_scan", "k_prep_segs"], "pileup": ["k_pileup_multi<false,false>"]}
+        under_profiler = any(os.environ.get(k) for k in ("HSA_TOOLS_LIB", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD", "ROCPROF_OUTPUT_PATH"))      # (this run is itself being profiled: no profiler inside a profiler)
+        if rank == 0 and world == 1 and not args.no_live_traffic and not under_profiler and not extra and not args.synth_args and args.length == 1_000_000 and shutil.which("rocprofv3"):
+            try:
+                import csv, glob
+                per = {}
+                for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
+                    pd = work / f"pmc_{ctr}"
+                    subprocess.run([shutil.which("rocprofv3"), "--kernel-trace", "--output-format", "csv", "--pmc", ctr, "-d", str(pd), "-o", "p", "--", sys.executable, str(REPO / "tools/prep_bench.py"), str(R)],
+                                   cwd="/tmp", env=dict(os.environ, PREP_BENCH_FAST="2", TMPDIR="/tmp"), capture_output=True, text=True, timeout=400)
+                    rows = {}
+                    for f in glob.glob(f"{pd}/**/*counter_collection.csv", recursive=True):
+                        for r in csv.DictReader(open(f)):
+                            if r["Counter_Name"] != ctr:
+                                continue
+                            k = re.sub(r"\(.*\)\s*$", "", re.sub(r"^void\s+", "", r["Kernel_Name"].strip())).replace(", ", ",").replace(" ", "")
+                            rows.setdefault(k, []).append((int(r["Grid_Size"]), float(r["Counter_Value"])))
+                    for k, v in rows.items():
+                        gmax = max(g for g, _ in v); big = [x for g, x in v if g >= 0.98 * gmax]
+                        per.setdefault(k, {})[ctr] = (sum(big) / len(big) * 1024.0, len(big))              # rocprofv3 reports KiB
+                ks = fam_kernels[dominant]
+                if all(k in per and "FETCH_SIZE" in per[k] and "WRITE_SIZE" in per[k] for k in ks):
+                    fr = sum(per[k]["FETCH_SIZE"][0] for k in ks); wr = sum(per[k]["WRITE_SIZE"][0] for k in ks)
+                    traffic = 2 * fr + wr
+                    traffic_info = {"measured": "live: rocprofv3 --pmc passes run by this bench.py invocation (tools/prep_bench.py: the same kernels on the same resident intervals, 8 chunks per launch)",
+                                    "kernels": ks, "dispatches": {k: per[k]["FETCH_SIZE"][1] for k in ks}, "fetch_raw_counter_bytes": fr, "write_raw_counter_bytes": wr,
+                                    "per_kernel": {k: {"fetch_x2_plus_write": 2 * per[k]["FETCH_SIZE"][0] + per[k]["WRITE_SIZE"][0]} for k in ks},
+                                    "note": "per launch, summed over the family's kernels: FETCH_SIZE x 2 (gfx950 tallies 128-byte requests as 64) + WRITE_SIZE"}
+            except Exception as ex:
+                log(f"[bench] live traffic counters failed: {ex!r}")
+        if traffic is None:
+            try:
+                # the round's final summary (rNNfin_*) if there is one, else the last one of the latest round by name
+                cand = sorted((REPO / "profiles").glob("r[0-9][0-9]*_rocprofv3_pmc_summary.json"), key=lambda q: (q.name[:3], "fin" in q.name.split("_")[0], q.name))
+                prof = json.load(open(cand[-1]))
+                k = prof["families"].get(dominant)
+                if k and not extra and not args.synth_args and args.length == 1_000_000 and k.get("chunks_per_launch") == GROUP:
+                    traffic = k["hbm_bytes_per_launch"]["fetch_x2_plus_write"]
+                    traffic_info = {"measured": "NOT this run: the committed summary of a separate profiled run", "file": cand[-1].name, "kernels": k["kernels"], "dispatches": k["dispatches"], "fetch_raw_counter_bytes": k["hbm_bytes_per_launch"]["fetch_raw"], "write_raw_counter_bytes": k["hbm_bytes_per_launch"]["write_raw"],
+                                    "note": "per launch, summed over the family's kernels: FETCH_SIZE x 2 (gfx950 tallies 128-byte requests as 64) + WRITE_SIZE"}
+            except Exception:
+                pass
 
     result = None
     if rank == 0:
@@ -743,20 +804,21 @@ def main():
                        "records_per_interval": raw_records // R, "record_bytes_per_interval": raw_bytes // R,
                        "reads_admitted_per_interval": reads // R, "segments_per_interval": segs // R, "records_per_gpu": synth_info["records"],
                        "sites_per_interval": int(n_sites_sum) // R, "cpg_calls_per_interval": int(cpg_calls) // R,
-                       "tile": int(br.tile), "tiles_per_launch": int(br.n_tiles), "lds_bytes_per_workgroup": int(br.lds_bytes),
                        "parallelism": f"interval-sharded x{n_gpus}" + (f" + gather of site buffers to rank 0 ({GROUP} chunks = one launch per exchange, {bytes_per_exchange} B per exchange and rank)" if world > 1 else ""),
                        "in_flight": "2 launches queued per GPU, in order on one stream (launch g is issued, then the chunks of launch g-1 are collected: their site counts read back with one copy); every launch is issued and collected inside the timed region"},
-            "roofline": dict(fam[dominant], family=dominant, traffic=traffic, traffic_source=traffic_info, chunks_per_launch=GROUP,
-                             measured=f"HIP events around launches of the family's kernels ({GROUP} resident 1 Mb chunks per launch) rotating over the {R} resident intervals on one stream",
-                             kernels=fam,
-                             step={"algo_bytes_per_chunk": step_bytes // GROUP, "device_ms_per_chunk": step_s / GROUP * 1e3, "achieved": step_bytes / step_s / 1e9 if step_s > 0 else 0.0, "unit": "GB/s",
-                                   "frac": step_bytes / step_s / 1e9 / HBM_PEAK_GBS if step_s > 0 else 0.0,
-                                   "note": "SURVEY.md 8d's algorithmic bytes of a chunk over the device time of its preparation + pileup (sum of the families' HIP-event times)"},
-                             pileup_one_chunk_per_launch={"kernel_ms": br_single.ms_pileup, "achieved": br_single.algo_bytes / (br_single.ms_pileup / 1e3) / 1e9 if br_single.ms_pileup > 0 else 0.0},
-                             pileup_cache_resident={"kernel_ms": br1.ms_pileup, "achieved": br1.algo_bytes / (br1.ms_pileup / 1e3) / 1e9 if br1.ms_pileup > 0 else 0.0,
-                                                    "note": "interval 0 relaunched back to back: its records stay in the 256 MiB Infinity Cache (the round-1 measurement)"}),
             "host_upload_s": t_host,
         }
+        if args.full:
+            result["config"].update(tile=int(br.tile), tiles_per_launch=int(br.n_tiles), lds_bytes_per_workgroup=int(br.lds_bytes))
+            result["roofline"] = dict(fam[dominant], family=dominant, traffic=traffic, traffic_source=traffic_info, chunks_per_launch=GROUP,
+                                      measured=f"HIP events around launches of the family's kernels ({GROUP} resident 1 Mb chunks per launch) rotating over the {R} resident intervals on one stream",
+                                      kernels=fam,
+                                      step={"algo_bytes_per_chunk": step_bytes // GROUP, "device_ms_per_chunk": step_s / GROUP * 1e3, "achieved": step_bytes / step_s / 1e9 if step_s > 0 else 0.0, "unit": "GB/s",
+                                            "frac": step_bytes / step_s / 1e9 / HBM_PEAK_GBS if step_s > 0 else 0.0,
+                                            "note": "SURVEY.md 8d's algorithmic bytes of a chunk over the device time of its preparation + pileup (sum of the families' HIP-event times)"},
+                                      pileup_one_chunk_per_launch={"kernel_ms": br_single.ms_pileup, "achieved": br_single.algo_bytes / (br_single.ms_pileup / 1e3) / 1e9 if br_single.ms_pileup > 0 else 0.0},
+                                      pileup_cache_resident={"kernel_ms": br1.ms_pileup, "achieved": br1.algo_bytes / (br1.ms_pileup / 1e3) / 1e9 if br1.ms_pileup > 0 else 0.0,
+                                                             "note": "interval 0 relaunched back to back: its records stay in the 256 MiB Infinity Cache (the round-1 measurement)"})
         if world > 1:
             result["exchange"] = {"exchanges": exchanges, "bytes_per_exchange_per_rank": bytes_per_exchange,
                                   "transport": f"NONE -- the ranks ran without the gather of site buffers to rank 0: {exchange_off}" if exchange_off else
@@ -766,13 +828,13 @@ def main():
         if dense:
             result["dense_contexts"] = dense
         log(f"[bench] device legs done in {time.time() - t_start:.0f} s")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
           try:
             e2e_legs(args, result, data, work, extra, headline, t_start, mdk)
           except Exception as ex:            # a leg that fails or hangs (timeout) must not take the measured line with it
             result["legs_error"] = repr(ex)[:500]
             log(f"[bench] a CPU/end-to-end leg failed: {ex!r}")
-        if world > 1 and not args.no_cpu_baseline:
+        if args.full and world > 1 and not args.no_cpu_baseline:
           try:
             ranks_leg(args, result, data, work, world, mdk, dist)
           except Exception as ex:

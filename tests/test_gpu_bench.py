@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 def run_bench(*extra):
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--passes", "2", "--no-cpu-baseline"] + list(extra),
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--passes", "2", "--full", "--no-cpu-baseline"] + list(extra),
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-4000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

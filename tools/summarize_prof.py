@@ -81,7 +81,7 @@ for fn, ks in fam.items():
         families[fn] = {"kernels": ks, "dispatches": [k["dispatches"] for k in have], "chunks_per_launch": chunks,
                         "duration_us_sum_of_kernel_averages": sum(dur[k]["avg_us"] for k in ks if k in dur) if all(k in dur for k in ks) else None,
                         "hbm_bytes_per_launch": {x: sum(k["hbm_bytes_per_launch"][x] for k in have) for x in ("fetch_raw", "write_raw", "fetch_x2_plus_write")}}
-out = {"command": "python bench.py --no-cpu-baseline --steps 2 --warmup 1 --passes 4 (16 resident 1 Mb intervals in rotation, ~0.9 GB of records; one rocprofv3 --pmc pass per counter group); only the dispatches with each kernel's largest grid (the 8-chunk launches) are averaged",
+out = {"command": "python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --passes 4 (16 resident 1 Mb intervals in rotation, ~0.9 GB of records; one rocprofv3 --pmc pass per counter group); only the dispatches with each kernel's largest grid (the 8-chunk launches) are averaged",
        "unit_note": "FETCH_SIZE / WRITE_SIZE are reported by rocprofv3 in KiB; fetch_x2_plus_write applies MI355X_MICROARCH.md's gfx950 correction (128-byte requests tallied as 64) to the fetch side only",
        "kernels": kernels, "families": families}
 json.dump(out, open(f"{dst}/{tag}_rocprofv3_pmc_summary.json", "w"), indent=1)
