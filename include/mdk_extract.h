@@ -132,6 +132,33 @@ int  mdk_plan_emit_perread_raw(mdk_plan *p, const mdk_chunk *c, const uint32_t *
  * its single-GPU commands; a library caller decides for itself.  No counterpart in the reference. */
 int  mdk_bind_to_device_node(int index);
 
+/* ---- a resident extract session: the calls as device-resident columns, one process across many runs ----
+ * mdk_session_extract takes the argv of extract_main (argv[0] = "extract"), parses it with the same code and returns the same codes for
+ * the same errors.  Instead of bedGraph files it returns the rows those files would hold (include/mdk_hip.h "calls on the device":
+ * contig, start, end, nmeth, nunmeth, context, strand).  Differences from the command:
+ *   - --fraction, --counts, --logit, --methylKit and --cytosine_report are refused with MDK_RC_UNSUPPORTED (they only shape text);
+ *   - -o is ignored and no output file is written; -O / -N (writing a BBM file) behave as in the command;
+ *   - MDK_RANK / MDK_WORLD are ignored: one device;
+ *   - the process is never left through _exit, and the HIP runtime and the device handle stay up between runs (md_dev_reset before
+ *     every run after the first: nothing of one run -- contigs, -l runs, mappability -- reaches the next).
+ * Ownership and lifetimes: a session owns its device handle until mdk_session_close.  Each successful mdk_session_extract returns a new
+ * mdk_calls (*out; NULL on error) that owns its rows in device memory and its contig names; it does not depend on the session and
+ * stays valid, also after mdk_session_close, until mdk_calls_free.  The calls of one session must come from one thread at a time.
+ * mdk_calls_contig_name's string belongs to the mdk_calls.  mdk_calls_copy is synchronous: `dst` (device memory of the session's device
+ * when to_host = 0, host memory when 1) holds mdk_calls_count entries of the column's type when it returns. */
+#define MDK_RC_UNSUPPORTED (-23)  /* an option a session does not take */
+typedef struct mdk_session mdk_session;
+typedef struct mdk_calls mdk_calls;
+enum { MDK_CALLS_CONTIG = 0, MDK_CALLS_START, MDK_CALLS_END, MDK_CALLS_NMETH, MDK_CALLS_NUNMETH, MDK_CALLS_CONTEXT, MDK_CALLS_STRAND };   /* int32 x5, uint8, int8 */
+int  mdk_session_open(int device, mdk_session **out);
+int  mdk_session_extract(mdk_session *s, int argc, char *argv[], mdk_calls **out);
+void mdk_session_close(mdk_session *s);
+int64_t mdk_calls_count(const mdk_calls *c);
+int  mdk_calls_n_contigs(const mdk_calls *c);
+const char *mdk_calls_contig_name(const mdk_calls *c, int i);
+int  mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host);
+void mdk_calls_free(mdk_calls *c);
+
 /* ---- `mergeContext` (mergeContext.c; main.c:19,53-54): text-to-text host tool, no device work ---- */
 int  mergeContext_main(int argc, char *argv[]);
 

@@ -324,6 +324,53 @@ int  md_dev_wait(md_dev *h, int slot, md_sites_dev *out);
 int64_t md_sites_order(const md_site *site, const md_site_var *var, const md_tile_seg *seg, int32_t n_tiles, int64_t n_slots,
                        md_site *out_site, md_site_var *out_var);
 
+/* ---- calls on the device (a resident extract session: include/mdk_extract.h mdk_session_*) ----
+ * What the text post-pass (csrc/host/mdk_emit.c emit_format) makes of a chunk's sites -- the variant filter, --mergeContext, the depth
+ * test, the contexts switched on -- done on the device (k_calls_compact), and the rows kept there as columns instead of printed:
+ *   start, end  (int32)  bedGraph columns 2 and 3: end = start + 1, or + 2 / + 3 for a merged CpG / CHG row
+ *   nmeth, nunmeth (int32)
+ *   context     (uint8)  0 CpG, 1 CHG, 2 CHH
+ *   strand      (int8)   +1 a C, -1 a G, 0 a --mergeContext CpG / CHG row (keyed at its C, whichever members survived)
+ *   contig      (int32)  the chunk's tid (BAM header order)
+ * Rows come in schedule order of the chunks (the keys given to md_dev_calls_group) and, within a chunk, in the order of the sites that
+ * make them: for each context that is ascending `start`, exactly the order of that context's bedGraph lines.  --cytosine_report rows are
+ * not made here.
+ * Sequence: md_dev_calls_begin, then for every collected group md_dev_calls_group in place of md_dev_download_group (a slot answered
+ * with MDK_ERR_PREP_HOST is prepared on the host, submitted again and passed to md_dev_calls_group alone, with its key), then
+ * md_dev_calls_finish.  Between begin and finish, group launches leave their sites on the device (no copy to pinned host memory), so
+ * md_dev_download_group must not be used on the handle meanwhile.  Single caller thread for the calls_* functions of a handle.
+ * Ownership: the handle keeps a row arena and a tile table in device memory (plain hipMalloc, grown by doubling, kept until
+ * md_dev_reset / md_dev_close); md_dev_calls_finish returns a md_calls_set that owns its own device memory, independent of the handle
+ * (it may outlive it), until md_calls_set_free. */
+typedef struct {
+    int32_t min_depth;             /* -d, >= 1 */
+    int32_t merge;                 /* --mergeContext */
+    int32_t min_opposite_depth;    /* --minOppositeDepth (0: no variant filter; the handle's cfg.minOppositeDepth must match) */
+    double  max_variant_frac;      /* --maxVariantFrac */
+    int32_t ctx_on[3];             /* CpG, CHG, CHH rows wanted */
+} md_calls_cfg;
+typedef struct md_calls_set md_calls_set;
+/* destination of md_calls_set_copy: n entries each; a NULL column is not copied */
+typedef struct { int32_t *contig, *start, *end, *nmeth, *nunmeth; uint8_t *context; int8_t *strand; } md_calls_cols;
+int  md_dev_calls_begin(md_dev *h, const md_calls_cfg *cfg);
+/* waits for the group (as md_dev_download_group), reserves each chunk's room and queues k_calls_compact on the handle's own stream; the
+ * slots' streams wait for it before their next work.  keys[i]: the chunk's place in the output order (its schedule index).  rc[i]: what
+ * md_dev_download would have returned for slots[i] (0, MDK_ERR_PREP_HOST, MDK_ERR_STRAND0, ...); only rc 0 chunks are compacted.
+ * Returns 0 when the collection itself worked. */
+int  md_dev_calls_group(md_dev *h, const int *slots, const uint32_t *keys, int n, int *rc);
+/* waits for every compaction, closes the gaps between the chunks' reservations (k_calls_gather) and hands the rows over */
+int  md_dev_calls_finish(md_dev *h, md_calls_set **out);
+int64_t md_calls_set_count(const md_calls_set *c);
+/* synchronous copies of the columns into DEVICE memory of the set's device (to_host = 0) or host memory (to_host = 1) */
+int  md_calls_set_copy(const md_calls_set *c, const md_calls_cols *dst, int to_host);
+void md_calls_set_free(md_calls_set *c);
+/* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
+ * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram and the calls state
+ * are dropped, every slot's buffers are given back.  Pointers the library returned for the handle before (md_sites, md_sites_dev,
+ * md_mbias) are void afterwards; md_piece objects must have been destroyed first.  When no other handle is open, the carved device
+ * memory is reused from its start (a handle used for run after run would otherwise keep taking more). */
+int  md_dev_reset(md_dev *h, const md_dev_cfg *cfg);
+
 /* Re-run the kernels of an uploaded slot `iters` times (inputs stay resident in HBM; results are identical
  * every time) and time them with HIP events on the slot's stream. */
 int  md_dev_bench(md_dev *h, int slot, int warmup, int iters, md_bench_result *out);

@@ -165,13 +165,15 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_set_prep", "md_dev_set_mappability", "md_dev_upload_raw", "md_dev_upload_raw_inplace", "md_dev_upload_wait", "md_dev_upload_done", "md_dev_submit_raw", "md_dev_debug_segments", "md_dev_bench_prep", "md_dev_bench_prep_rotate", "md_bench_set_prep",
                "md_dev_mbias_submit", "md_dev_mbias_submit_raw", "md_dev_mbias_read", "md_dev_mbias_reset", "md_dev_slot_sync",
                "md_dev_perread_submit", "md_dev_perread_download", "md_dev_perread_submit_raw", "md_dev_perread_download_raw", "md_dev_read_raw",
-               "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc"]
+               "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
+               "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
                    "mdk_plan_host_prepare_from", "mdk_plan_release_records", "mdk_plan_attach_device", "mdk_plan_detach_device",
                    "mbias_main", "mdk_cli_quiesce", "mdk_plan_open_mbias", "mdk_plan_mbias_outputs", "mdk_mbias_report",
-                   "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node"]
+                   "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node",
+                   "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free"]
 
 _hip = None
 _ext = None
@@ -621,3 +623,111 @@ def run_ranks(args, n, cwd=None, env=None, command="extract", devices=None, time
     cp.rank_returncodes = [p_.returncode for p_ in procs]
     cp.rank_stderr = [(o or ("", ""))[1] for o in outs]
     return cp
+
+
+# ---- a resident extract session: the calls as tensors (include/mdk_extract.h mdk_session_*) ----
+RC_UNSUPPORTED = -23
+CALL_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("context", "uint8"), ("strand", "int8"))
+
+
+def _session_lib():
+    L = lib_extract()
+    if not getattr(L, "_session_types", False):
+        L.mdk_session_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.mdk_session_extract.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+        L.mdk_session_close.argtypes = [C.c_void_p]
+        L.mdk_calls_count.argtypes = [C.c_void_p]
+        L.mdk_calls_count.restype = C.c_int64
+        L.mdk_calls_n_contigs.argtypes = [C.c_void_p]
+        L.mdk_calls_contig_name.argtypes = [C.c_void_p, C.c_int]
+        L.mdk_calls_contig_name.restype = C.c_char_p
+        L.mdk_calls_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.mdk_calls_free.argtypes = [C.c_void_p]
+        L._session_types = True
+    return L
+
+
+class Calls:
+    """The rows `extract` would print, as columns (one entry per call, in the order of the chunks of the schedule; within a context,
+    ascending `start`): ``contig`` (int32, index into ``contigs``, BAM header order), ``start``/``end`` (int32, bedGraph columns 2-3),
+    ``nmeth``/``nunmeth`` (int32), ``context`` (uint8: 0 CpG, 1 CHG, 2 CHH) and ``strand`` (int8: +1 C, -1 G, 0 a --mergeContext row)."""
+
+    def __init__(self, contigs, columns):
+        self.contigs = contigs
+        for name, _ in CALL_COLUMNS:
+            setattr(self, name, columns[name])
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    def rows(self, context=None):
+        """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
+        cols = [getattr(self, n).cpu().tolist() for n in ("contig", "start", "end", "nmeth", "nunmeth", "context")]
+        return [(self.contigs[c], a, b, m, u) for c, a, b, m, u, x in zip(*cols) if context is None or x == context]
+
+
+class Session:
+    """One process, one device handle, many `extract` runs: ``Session(device=0).extract(args) -> Calls``.  ``args`` is the extract
+    command line as for run_cli (without the command name).  The rows never pass through text: they are compacted on the device
+    (k_calls_compact) and copied device to device into tensors torch allocated on ``torch.device("cuda", device)``; with
+    ``device_tensors=False`` into CPU tensors instead.  --fraction/--counts/--logit/--methylKit/--cytosine_report are refused (rc -23),
+    -o is ignored; any non-zero return code raises MdkError with ``.rc``."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+        self._L = _session_lib()
+        h = C.c_void_p()
+        rc = self._L.mdk_session_open(int(device), C.byref(h))
+        if rc:
+            raise _rc_error("mdk_session_open", rc)
+        self._h = h
+
+    def extract(self, args, device_tensors: bool = True) -> Calls:
+        import torch
+        if self._h is None:
+            raise MdkError("the session is closed")
+        argv = ["extract"] + [str(a) for a in args]
+        arr = (C.c_char_p * (len(argv) + 1))(*[a.encode() for a in argv], None)
+        out = C.c_void_p()
+        rc = self._L.mdk_session_extract(self._h, len(argv), arr, C.byref(out))
+        if rc:
+            raise _rc_error("extract", rc)
+        try:
+            n = int(self._L.mdk_calls_count(out))
+            contigs = [self._L.mdk_calls_contig_name(out, i).decode() for i in range(self._L.mdk_calls_n_contigs(out))]
+            dev = torch.device("cuda", self.device) if device_tensors else torch.device("cpu")
+            cols = {}
+            for k, (name, dt) in enumerate(CALL_COLUMNS):
+                t = torch.empty(n, dtype=getattr(torch, dt), device=dev)
+                if n:
+                    rc = self._L.mdk_calls_copy(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
+                    if rc:
+                        raise _rc_error(f"copying the {name} column", rc)
+                cols[name] = t
+        finally:
+            self._L.mdk_calls_free(out)
+        return Calls(contigs, cols)
+
+    def close(self):
+        if self._h is not None:
+            self._L.mdk_session_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _rc_error(what, rc):
+    msg = "option not available through a session" if rc == RC_UNSUPPORTED else MDK_ERR.get(rc, "see stderr")
+    e = MdkError(f"{what} failed: rc {rc} ({msg})")
+    e.rc = rc
+    return e

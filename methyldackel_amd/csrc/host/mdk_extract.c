@@ -87,6 +87,7 @@ enum { G_FREE = 0, G_FILL, G_LAUNCHED };
 typedef struct { mdk_chunk ch[MDK_GROUP]; int slot[MDK_GROUP]; int n, launched[MDK_GROUP], inplace[MDK_GROUP], state, held, n_held, rel_slot[MDK_GROUP]; mdk_chunk rel_ch[MDK_GROUP]; } cgroup;      /* held: the host memory behind its records has not been given back yet; inplace: the device reads the chunk's records where the piece they were inflated in holds them (md_dev_upload_raw_inplace): that piece goes back when the chunk's results are in */
 typedef struct {
     mdk_plan *p; md_dev *dev; emitter *em; cgroup G[MDK_NGROUPS_MAX];
+    int calls;                           /* the sink of collected groups: 0 the text emitter (extract_main), 1 the device calls of a session (md_dev_calls_group) */
     pthread_mutex_t mu; pthread_cond_t cv;
     int ret, up_done;                    /* (mu) first error; the uploader has launched its last group */
     uint64_t n_up, n_col;                /* (mu) groups launched / collected: group k lives in G[k % MDK_NGROUPS] */
@@ -165,7 +166,8 @@ static void *collector_main(void *arg) {
         memset(sites, 0, sizeof(sites));
         for(i = 0; i < g->n; i++) if(g->launched[i]) { ls[nl] = g->slot[i]; li[nl] = i; nl++; }
         ta = now_s(); g_col_phase = 1;
-        if(nl) rc = md_dev_download_group(dev, ls, nl, st, rcs);
+        if(nl && X->calls) { uint32_t keys[MDK_GROUP]; for(i = 0; i < nl; i++) keys[i] = g->ch[li[i]].index; rc = md_dev_calls_group(dev, ls, keys, nl, rcs); }
+        else if(nl) rc = md_dev_download_group(dev, ls, nl, st, rcs);
         g_col_phase = 2;
         if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); xp_fail(X, MDK_RC_DEVICE); break; }
         for(i = 0; i < nl && !bad; i++) {
@@ -176,7 +178,8 @@ static void *collector_main(void *arg) {
                 if(!told) { told = 1; fprintf(stderr, "[mdk] note: a chunk holds a read name with more records than the device preparation handles (secondary/supplementary-rich or amplicon-like data); such chunks are prepared on the host, which is slower\n"); }
                 rc = mdk_plan_host_prepare_from(p, &g->ch[k], dev, g->slot[k]);
                 if(!rc) rc = md_dev_submit(dev, g->slot[k], &g->ch[k].batch);
-                if(!rc) rc = md_dev_download(dev, g->slot[k], &st[i]);
+                if(!rc && X->calls) { int rc1 = 0; rc = md_dev_calls_group(dev, &g->slot[k], &g->ch[k].index, 1, &rc1); if(!rc) rc = rc1; }
+                else if(!rc) rc = md_dev_download(dev, g->slot[k], &st[i]);
                 X->n_host_prep++;
             }
             if(rc == MDK_ERR_STRAND0) { fprintf(stderr, "Can't determine the strand of a read!\n"); abort(); }
@@ -186,6 +189,7 @@ static void *collector_main(void *arg) {
         }
         X->w_down += now_s() - ta;
         if(bad) break;
+        if(X->calls) { g_col_phase = 0; pthread_mutex_lock(&X->mu); g->n = 0; g->state = G_FREE; X->n_col++; pthread_cond_broadcast(&X->cv); pthread_mutex_unlock(&X->mu); continue; }      /* the rows stay on the device */
         ta = now_s();
         g_col_phase = 3;
         for(i = 0; i < g->n; i++) if(emitter_push_lazy(X->em, &g->ch[i], &sites[i])) { xp_fail(X, X->em->failed ? MDK_RC_OUTPUT : MDK_RC_DEVICE); bad = 1; break; }
@@ -212,14 +216,32 @@ static void xopen_start(mdk_plan *p, void *arg) {
     o->started = pthread_create(&o->th, NULL, devopen_main, &o->d) == 0;
 }
 
-int extract_main(int argc, char *argv[]) {
+/* ---- a resident session (include/mdk_extract.h): the same pipeline, one device handle across runs, calls kept on the device ---- */
+struct mdk_session { int device; md_dev *dev; md_dev_cfg cfg; };
+struct mdk_calls { md_calls_set *set; int64_t n; int n_contigs; char **names; };
+/* the session's after_options: options that only shape text or files are refused; the device configuration is worked out as for the command */
+static void session_options(mdk_plan *p, void *arg) {
+    xopen *o = arg; const opts_t *q = &p->o;
+    p->no_text = 1;
+    if(q->fraction || q->counts || q->logit || q->methylkit || q->cytosine_report) {
+        fprintf(stderr, "[mdk] --fraction, --counts, --logit, --methylKit and --cytosine_report only shape text output: a session returns the calls themselves\n");
+        p->open_rc = MDK_RC_UNSUPPORTED; return;
+    }
+    if(getenv("MDK_GROUPS_IN_FLIGHT")) { g_ngroups = atoi(getenv("MDK_GROUPS_IN_FLIGHT")); if(g_ngroups < 2) g_ngroups = 2; if(g_ngroups > MDK_NGROUPS_MAX) g_ngroups = MDK_NGROUPS_MAX; }
+    else g_ngroups = 3;
+    mdk_plan_dev_cfg(p, &o->d.cfg);
+    o->d.cfg.n_slots = MDK_NGROUPS * MDK_GROUP; o->d.cfg.n_streams = MDK_NGROUPS;
+}
+
+/* extract_main's pipeline; S != NULL: a session's run -- no output files, no emitter, every collected group compacted into calls on S's device
+ * handle (opened at the first run, reset before every later one), handed over in *out */
+static int extract_run(int argc, char *argv[], mdk_session *S, mdk_calls **out) {
     mdk_plan *p = NULL; md_dev *dev = NULL; xpipe *X = NULL; int rc, ret = 0, more = 1, i, g_i; xopen dop; pthread_t cth, rth, preg; int cth_ok = 0, rth_ok = 0, preg_ok = 0; emitter em;
     double T0 = now_s(), t_open, t_dev, w_next = 0, w_sub = 0, w_group = 0, w_ref = 0, w_rel = 0, ta; uint64_t n_chunks = 0; int32_t ref_t0, ref_t1;
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] entered at epoch %.3f\n", ts.tv_sec + 1e-9 * ts.tv_nsec); }
-    { int rk = 0, wd = 1, m = ranks_from_env(&rk, &wd); if(m < 0) return -1; if(m > 0) return extract_ranks(argc, argv, rk, wd); }       /* one process per GPU (mdk_ranks.c) */
-    if(argc > 2) hip_warm_up();
-    memset(&dop, 0, sizeof(dop));
-    rc = plan_open_ex(argc, argv, &p, xopen_start, &dop);
+    if(argc > 2 && !S) hip_warm_up();
+    memset(&dop, 0, sizeof(dop)); memset(&em, 0, sizeof(em));
+    rc = plan_open_ex(argc, argv, &p, S ? session_options : xopen_start, &dop);
     t_open = now_s() - T0;
     if(rc != 0 || !p) { if(dop.started) { pthread_join(dop.th, NULL); if(dop.d.dev) md_dev_close(dop.d.dev); } return rc; }
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] resident after plan open %.0f MB\n", rss_mb(0));
@@ -229,7 +251,13 @@ int extract_main(int argc, char *argv[]) {
     if(!getenv("MDK_HOST_PREP")) mdk_plan_set_prep(p, 1);
     mdk_plan_set_hold(p, MDK_NGROUPS * MDK_GROUP + 2);
     if(!p->started && pipeline_start(p)) { if(dop.started) pthread_join(dop.th, NULL); if(dop.d.dev) md_dev_close(dop.d.dev); mdk_plan_close(p); return -5; }
-    if(dop.started) pthread_join(dop.th, NULL); else { xopen_start(p, &dop); if(dop.started) pthread_join(dop.th, NULL); else devopen_main(&dop.d); }
+    if(S) {          /* the session's handle: opened once, then reset to this run's configuration */
+        dop.d.device = S->device;
+        if(S->dev && (S->cfg.n_slots != dop.d.cfg.n_slots || S->cfg.n_streams != dop.d.cfg.n_streams)) { md_dev_close(S->dev); S->dev = NULL; }
+        if(S->dev) { dop.d.rc = md_dev_reset(S->dev, &dop.d.cfg); dop.d.dev = S->dev; if(dop.d.rc) { snprintf(dop.d.err, sizeof(dop.d.err), "%s", md_dev_last_error()); md_dev_close(S->dev); S->dev = dop.d.dev = NULL; } }
+        else devopen_main(&dop.d);
+        S->dev = dop.d.dev; S->cfg = dop.d.cfg;
+    } else if(dop.started) pthread_join(dop.th, NULL); else { xopen_start(p, &dop); if(dop.started) pthread_join(dop.th, NULL); else devopen_main(&dop.d); }
     t_dev = now_s() - T0;
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] resident at device ready %.0f MB\n", rss_mb(0));
     dev = dop.d.dev;
@@ -239,8 +267,15 @@ int extract_main(int argc, char *argv[]) {
     if(p->dev_prep) mdk_plan_attach_device(p, dev);      /* from here on the device inflates pieces of the file too */
     X = calloc(1, sizeof(*X));
     if(X) X->ref_state = calloc((size_t)p->bam->n_targets + 1, sizeof(int));
-    if(!X || !X->ref_state || emitter_start(&em, p, emit_threads(p))) { if(X) free(X->ref_state); free(X); mdk_plan_detach_device(p); md_dev_close(dev); mdk_plan_close(p); return -5; }
-    X->p = p; X->dev = dev; X->em = &em; X->ref_t0 = ref_t0; X->ref_t1 = ref_t1; pthread_mutex_init(&X->mu, NULL); pthread_cond_init(&X->cv, NULL);
+    if(X && S) {     /* the session's sink: the calls configuration is the text post-pass's */
+        md_calls_cfg cc; memset(&cc, 0, sizeof(cc));
+        cc.min_depth = p->o.min_depth; cc.merge = p->o.merge; cc.min_opposite_depth = p->o.min_opp_depth > 0 ? p->o.min_opp_depth : 0; cc.max_variant_frac = p->o.max_variant_frac;
+        for(i = 0; i < 3; i++) cc.ctx_on[i] = p->o.ctx_on[i];
+        X->calls = 1;
+        if(md_dev_calls_begin(dev, &cc)) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); free(X->ref_state); free(X); mdk_plan_detach_device(p); mdk_plan_close(p); return MDK_RC_DEVICE; }
+    }
+    if(!X || !X->ref_state || (!S && emitter_start(&em, p, emit_threads(p)))) { if(X) free(X->ref_state); free(X); mdk_plan_detach_device(p); if(!S) md_dev_close(dev); mdk_plan_close(p); return -5; }
+    X->p = p; X->dev = dev; X->em = S ? NULL : &em; X->ref_t0 = ref_t0; X->ref_t1 = ref_t1; pthread_mutex_init(&X->mu, NULL); pthread_cond_init(&X->cv, NULL);
     for(g_i = 0; g_i < MDK_NGROUPS; g_i++) for(i = 0; i < MDK_GROUP; i++) X->G[g_i].slot[i] = g_i * MDK_GROUP + i;
     preg_ok = !getenv("MDK_NO_PREREG") && pthread_create(&preg, NULL, prereg_main, dev) == 0;
     rth_ok = pthread_create(&rth, NULL, refs_main, X) == 0;
@@ -313,19 +348,78 @@ int extract_main(int argc, char *argv[]) {
     if(rth_ok) pthread_join(rth, NULL);
     if(preg_ok) pthread_join(preg, NULL);
     if(!ret) ret = X->ret;
-    { double tw = now_s(); emitter_stop(&em); X->w_emit += now_s() - tw; }
+    if(!S) { double tw = now_s(); emitter_stop(&em); X->w_emit += now_s() - tw; }
     if(em.failed && !ret) ret = MDK_RC_OUTPUT;
     if(getenv("MDK_HOST_PROFILE")) { double rs = 0; uint64_t rc2 = 0, rb = 0; md_host_profile(&rs, &rc2, &rb); fprintf(stderr, "[mdk main] staging blocks registered: %" PRIu64 " (%.0f MB) in %.3fs; %" PRIu64 " chunks in %" PRIu64 " group launches\n", rc2, rb / 1048576.0, rs, n_chunks, X->n_up); }
     if(getenv("MDK_HOST_PROFILE")) { char pt[1024]; if(md_dev_profile_text(pt, sizeof(pt)) == 0) fprintf(stderr, "[mdk hip] host threads inside the device library: %s\n", pt); }
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] plan open %.3fs, device ready at %.3fs, uploader: wait-for-chunk %.3fs wait-for-reference %.3fs wait-for-group %.3fs submit %.3fs wait-for-uploads %.3fs; collector: download %.3fs emit %.3fs, total %.3fs; chunks prepared on the host after all: %d\n", t_open, t_dev, w_next, w_ref, w_group, w_sub, w_rel, X->w_down, X->w_emit, now_s() - T0, X->n_host_prep);
-    if(ret == 0) mdk_plan_finish(p);
+    if(S) {          /* the rows, in schedule order, handed over with the contig names; the handle's calls state is finished either way */
+        md_calls_set *set = NULL; const int frc = md_dev_calls_finish(dev, &set);
+        if(!ret && frc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; }
+        if(!ret) {
+            mdk_calls *c = calloc(1, sizeof(*c)); const int nt = p->bam->n_targets;
+            if(c) c->names = calloc((size_t)nt + 1, sizeof(char *));
+            if(!c || !c->names) { free(c); md_calls_set_free(set); ret = -5; }
+            else { c->set = set; c->n = md_calls_set_count(set); c->n_contigs = nt; for(i = 0; i < nt; i++) c->names[i] = strdup(p->bam->target_name[i]); *out = c; }
+        } else md_calls_set_free(set);
+    } else if(ret == 0) mdk_plan_finish(p);
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] leaving at epoch %.3f (resident %.0f MB, of which file-backed/shared %.0f MB)\n", ts.tv_sec + 1e-9 * ts.tv_nsec, rss_mb(0), rss_mb(1)); }
-    if(fast_exit_wanted()) leave_fast_plan(p, ret);
+    if(!S && fast_exit_wanted()) leave_fast_plan(p, ret);
     { double tc = now_s(), td;
       pthread_mutex_destroy(&X->mu); pthread_cond_destroy(&X->cv); free(X->ref_state); free(X);
       mdk_plan_detach_device(p);
-      md_dev_close(dev); td = now_s();
+      if(!S) md_dev_close(dev);
+      td = now_s();
       mdk_plan_close(p);
       if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] device closed in %.3fs, plan (slabs, reference, mapped file) in %.3fs\n", td - tc, now_s() - td); }
     return ret;
+}
+
+int extract_main(int argc, char *argv[]) {
+    { int rk = 0, wd = 1, m = ranks_from_env(&rk, &wd); if(m < 0) return -1; if(m > 0) return extract_ranks(argc, argv, rk, wd); }       /* one process per GPU (mdk_ranks.c) */
+    return extract_run(argc, argv, NULL, NULL);
+}
+
+int mdk_session_open(int device, mdk_session **out) {
+    mdk_session *s;
+    if(!out || device < 0) return MDK_ERR_ARG;
+    *out = NULL;
+    if(!(s = calloc(1, sizeof(*s)))) return -5;
+    s->device = device;
+    *out = s;
+    return 0;
+}
+int mdk_session_extract(mdk_session *s, int argc, char *argv[], mdk_calls **out) {
+    int rc;
+    if(!s || !out || argc < 1 || !argv) return MDK_ERR_ARG;
+    *out = NULL;
+    rc = extract_run(argc, argv, s, out);
+    if(rc == 0 && !*out) { *out = calloc(1, sizeof(mdk_calls)); if(!*out) return -5; }      /* (help / version: no run, no calls) */
+    return rc;
+}
+void mdk_session_close(mdk_session *s) { if(!s) return; if(s->dev) md_dev_close(s->dev); free(s); }
+int64_t mdk_calls_count(const mdk_calls *c) { return c ? c->n : -1; }
+int mdk_calls_n_contigs(const mdk_calls *c) { return c ? c->n_contigs : -1; }
+const char *mdk_calls_contig_name(const mdk_calls *c, int i) { return (c && i >= 0 && i < c->n_contigs) ? c->names[i] : NULL; }
+int mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host) {
+    md_calls_cols d; memset(&d, 0, sizeof(d));
+    if(!c || !dst || column < 0 || column > MDK_CALLS_STRAND) return MDK_ERR_ARG;
+    if(!c->set || c->n == 0) return 0;
+    switch(column) {
+    case MDK_CALLS_CONTIG: d.contig = dst; break;
+    case MDK_CALLS_START: d.start = dst; break;
+    case MDK_CALLS_END: d.end = dst; break;
+    case MDK_CALLS_NMETH: d.nmeth = dst; break;
+    case MDK_CALLS_NUNMETH: d.nunmeth = dst; break;
+    case MDK_CALLS_CONTEXT: d.context = dst; break;
+    default: d.strand = dst; break;
+    }
+    return md_calls_set_copy(c->set, &d, to_host);
+}
+void mdk_calls_free(mdk_calls *c) {
+    int i;
+    if(!c) return;
+    md_calls_set_free(c->set);
+    for(i = 0; i < c->n_contigs; i++) free(c->names[i]);
+    free(c->names); free(c);
 }

@@ -311,7 +311,7 @@ MDK_LOCAL int plan_attach_inputs(mdk_plan *p, char *argv[], int first_positional
         for(i = 0; i < p->bam->n_targets; i++) { uint32_t k; p->map_of_tid[i] = -1; for(k = 0; k < p->map_n; k++) if(!strcmp(p->map_names[k], p->bam->target_name[i])) { p->map_of_tid[i] = (int)k; break; } }
     }
 
-    if(o->mbias || o->perread) goto region;
+    if(o->mbias || o->perread || p->no_text) goto region;
     /* output files and headers (extract.c:1343-1439) */
     if(!o->opref) {
         char *dot; o->opref = xstrdup(o->bam_name); dot = strrchr(o->opref, '.'); if(dot) *dot = 0;
@@ -476,7 +476,7 @@ MDK_LOCAL int plan_open_ex(int argc, char *argv[], mdk_plan **out, void (*after_
         return rc;
     }
 
-    if(after_options) after_options(p, ctx);
+    if(after_options) { after_options(p, ctx); if(p->open_rc) { int rc = p->open_rc; plan_free(p); return rc; } }
     { int rc = plan_attach_inputs(p, argv, optind); if(rc) return rc; }
     *out = p;
     return 0;

@@ -120,6 +120,8 @@ struct mdk_plan {
     double t_collect, t_pair, t_segs, t_emit, t_rfill, t_rwait, t_widle, t_wbusy;      /* MDK_HOST_PROFILE=1: seconds per host stage */
     /* device references already uploaded: (dev handle, tid) pairs */
     md_dev **ref_dev; int32_t *ref_tid; int n_ref, cap_ref;
+    int no_text;                       /* a session (mdk_session_extract): no output files are opened, the calls stay on the device */
+    int open_rc;                       /* set by plan_open_ex's after_options callback: the command line is refused with this return code */
 };
 
 

@@ -93,6 +93,12 @@ void arena_give(void *p) {
         }
     }
 }
+// md_dev_reset: the handle has given back everything it carved and is the only one open -- carving starts over in the blocks there are
+static void arena_restart_if_idle(int dev) {
+    if(dev < 0 || dev >= 16) return;
+    Arena &A = g_arena[dev]; std::lock_guard<std::mutex> lk(A.mu);
+    if(A.live == 0 && g_open_handles.load() <= 1) { A.cur = 0; A.used = 0; }
+}
 struct CallMark { std::atomic<const char *> what{nullptr}; std::atomic<double> t0{0}; };
 static CallMark g_marks[256]; static std::atomic<int> g_mark_next{0};
 static thread_local int t_mark_base = -1, t_mark_depth = 0;
@@ -136,6 +142,10 @@ static void harena_reserve(size_t n_blocks) {
         if(hipHostMalloc((void **)&b, HARENA_BLOCK, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return; }
         std::lock_guard<std::mutex> lk(A.mu); A.blocks.push_back(b);
     }
+}
+static void harena_restart_if_idle() {
+    HArena &A = g_harena; std::lock_guard<std::mutex> lk(A.mu);
+    if(A.live == 0 && g_open_handles.load() <= 1) { A.cur = 0; A.used = 0; }
 }
 void harena_give(void *p) {
     HArena &A = g_harena;
@@ -1057,18 +1067,21 @@ extern "C" int md_dev_open(int device, const md_dev_cfg *cfg, md_dev **out) {
 }
 
 static void ref_release(md_dev *h, size_t tid);
+static void slot_buffers_release(Slot &s) {
+    s.d_seg_in.release(); s.d_blob.release(); s.d_tiles.release(); s.h_tiles.release();
+    s.d_raw.release(); s.d_recoff.release(); s.d_prd.release(); s.d_zero.release();
+    s.d_aidx.release(); s.h_aidx.release(); s.d_hnext.release(); s.h_rectab.release();
+    s.d_pr.release(); s.d_cig.release(); s.d_prc.release(); s.h_prc.release();
+    s.d_site.release(); s.d_var.release(); s.d_seg.release();
+    s.h_site.release(); s.h_sorted.release(); s.h_var.release(); s.h_vsorted.release(); s.h_seg.release();
+}
 extern "C" void md_dev_close(md_dev *h) {
     if(!h) return;
     side_join(false);
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     for(auto &s : h->slots) {
-        s.d_seg_in.release(); s.d_blob.release(); s.d_tiles.release(); s.h_tiles.release();
-        s.d_raw.release(); s.d_recoff.release(); s.d_prd.release(); s.d_zero.release();
-        s.d_aidx.release(); s.h_aidx.release(); s.d_hnext.release(); s.h_rectab.release();
-        s.d_pr.release(); s.d_cig.release(); s.d_prc.release(); s.h_prc.release();
-        s.d_site.release(); s.d_var.release(); s.d_seg.release();
-        s.h_site.release(); s.h_sorted.release(); s.h_var.release(); s.h_vsorted.release(); s.h_seg.release();
+        slot_buffers_release(s);
         if(s.e0) (void)hipEventDestroy(s.e0); if(s.e1) (void)hipEventDestroy(s.e1); if(s.k0) (void)hipEventDestroy(s.k0); if(s.k1) (void)hipEventDestroy(s.k1);
     }
     for(hipStream_t st : h->streams) if(st) (void)hipStreamDestroy(st);
@@ -1077,6 +1090,7 @@ extern "C" void md_dev_close(md_dev *h) {
     if(h->piece_inf) (void)hipStreamDestroy(h->piece_inf);
     if(h->ref_stream) (void)hipStreamDestroy(h->ref_stream);
     g_open_handles.fetch_sub(1);                       // (before the last carved buffers go: the give that brings the count to zero may start the blocks over)
+    calls_state_free(h);
     h->d_status.release(); h->h_status.release();
     if(h->d_crc) (void)hipFree(h->d_crc);
     if(h->d_hist) (void)hipFree(h->d_hist);
@@ -1084,6 +1098,55 @@ extern "C" void md_dev_close(md_dev *h) {
     for(md_region *p : h->d_runs) if(p) (void)hipFree(p);
     for(size_t t = 0; t < h->ref.size(); t++) ref_release(h, t);
     delete h;
+}
+
+// An idle handle back to what md_dev_open left (a resident service runs one command after another on it): every slot's buffers, the
+// contigs (bases, -l runs, mappability), the preparation settings and the mbias histogram go; streams, events and the loaded code object
+// stay.  When this is the only open handle and nothing else is carved, the carved blocks are reused from their start afterwards -- a
+// handle that stayed open would otherwise take fresh carved memory for every run's pieces and slots.
+extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
+    if(!h || !cfg) return fail(MDK_ERR_ARG, "md_dev_reset", hipSuccess);
+    const int ns = cfg->n_slots > 0 ? cfg->n_slots : 2;
+    if(ns != h->n_slots || cfg->n_streams != h->cfg.n_streams) return fail(MDK_ERR_ARG, "md_dev_reset: another number of slots or streams needs md_dev_close + md_dev_open", hipSuccess);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    for(size_t t = 0; t < h->ref.size(); t++) ref_release(h, t);
+    h->ref.clear(); h->refcode.clear(); h->reflen.clear(); h->ref_carved.clear(); h->refcap.clear();
+    for(uint32_t *p : h->mapbits) if(p) (void)hipFree(p);
+    h->mapbits.clear(); h->maplen.clear();
+    for(md_region *p : h->d_runs) if(p) (void)hipFree(p);
+    h->d_runs.clear(); h->n_runs.clear(); h->has_runs.clear();
+    memset(&h->prep, 0, sizeof(h->prep)); h->prep_set = false;
+    if(h->d_hist) (void)hipFree(h->d_hist);
+    h->d_hist = nullptr; h->hist_cap = 0; h->hist_len = 0; h->h_hist.clear();
+    if(h->calls) { calls_state_free(h); }
+    h->no_pack = false;
+    for(Slot &s : h->slots) {
+        slot_buffers_release(s);
+        Slot f;                           // the slot as md_dev_open made it: its stream, events and status block stay
+        f.stream = s.stream; f.e0 = s.e0; f.e1 = s.e1; f.k0 = s.k0; f.k1 = s.k1; f.index = s.index; f.run = s.stream; f.ring = s.ring;
+        s = f;
+    }
+    h->d_status.release(); h->h_status.release();
+    arena_restart_if_idle(h->device); harena_restart_if_idle();
+    if(h->d_status.need((size_t)h->n_slots) || h->h_status.need((size_t)h->n_slots)) return MDK_ERR_NOMEM;
+    HIPCHK(hipMemset(h->d_status.p, 0, sizeof(SlotStatus) * (size_t)h->n_slots));
+    HIPCHK(hipDeviceSynchronize());
+    memset(h->h_status.p, 0, sizeof(SlotStatus) * (size_t)h->n_slots);
+    for(Slot &s : h->slots) { s.d_total.p = h->d_status.p[s.index].total; s.d_err.p = &h->d_status.p[s.index].err; s.d_pcnt.p = &h->d_status.p[s.index].pc; s.h_st.p = &h->h_status.p[s.index]; }
+    // the geometry this cfg implies, as md_dev_open sets it
+    h->cfg = *cfg;
+    h->tile = cfg->tile > 0 ? cfg->tile : ((cfg->keepCHG || cfg->keepCHH) ? 1536 : DEFAULT_TILE);
+    h->tile = (h->tile + WG - 1) / WG * WG;
+    if(h->tile > MAX_TILE) h->tile = MAX_TILE;
+    h->variant = cfg->minOppositeDepth > 0;
+    h->qw = (cfg->keepCHG || cfg->keepCHH) && !getenv("MDK_NO_QW");
+    while(fixed_lds(h->tile, h->variant) > LDS_LIMIT - 1024 && h->tile > WG) h->tile -= WG;
+    if(fixed_lds(h->tile, h->variant) > 65536) {
+        HIPCHK(hipFuncSetAttribute(pileup_fn(h->variant, h->qw), hipFuncAttributeMaxDynamicSharedMemorySize, fixed_lds(h->tile, h->variant)));
+        HIPCHK(hipFuncSetAttribute(pileup_multi_fn(h->variant, h->qw), hipFuncAttributeMaxDynamicSharedMemorySize, fixed_lds(h->tile, h->variant)));
+    }
+    return 0;
 }
 
 extern "C" int md_dev_tile(const md_dev *h) { return h ? h->tile : MDK_ERR_ARG; }
@@ -1112,16 +1175,18 @@ extern "C" int md_dev_set_reference(md_dev *h, int32_t tid, const char *seq, int
     HIPCHK(hipSetDevice(h->device));
     if((size_t)tid >= h->ref.size()) { h->ref.resize(tid + 1, nullptr); h->refcode.resize(tid + 1, nullptr); h->reflen.resize(tid + 1, 0); }
     if(h->ref_carved.size() < h->ref.size()) h->ref_carved.resize(h->ref.size(), 0);
-    ref_release(h, tid);
+    if(h->refcap.size() < h->ref.size()) h->refcap.resize(h->ref.size(), 0);
     char *d = nullptr; uint8_t *c = nullptr; bool carved = false;
-    if((size_t)len + 16 < ARENA_MAX) { d = (char *)arena_take((size_t)len + 16); c = d ? (uint8_t *)arena_take((size_t)len + 16) : nullptr; if(d && !c) { arena_give(d); d = nullptr; } carved = d != nullptr; }      // (made ahead by the warm-up: no allocation next to the pieces' copies)
-    if(!carved) {
+    if(h->ref[tid] && h->ref_carved[tid] && h->refcap[tid] >= len + 16) { d = h->ref[tid]; c = h->refcode[tid]; carved = true; h->ref[tid] = nullptr; h->refcode[tid] = nullptr; }      // the contig again: its carved arrays are reused (carved memory is not given back while the handle is open)
+    else ref_release(h, tid);
+    if(!d && (size_t)len + 16 < ARENA_MAX) { d = (char *)arena_take((size_t)len + 16); c = d ? (uint8_t *)arena_take((size_t)len + 16) : nullptr; if(d && !c) { arena_give(d); d = nullptr; } carved = d != nullptr; }      // (made ahead by the warm-up: no allocation next to the pieces' copies)
+    if(!d) {
         hipError_t e = hipMalloc((void **)&d, (size_t)len + 16);
         if(e != hipSuccess) return fail(MDK_ERR_NOMEM, "hipMalloc(reference)", e);
         e = hipMalloc((void **)&c, (size_t)len + 16);
         if(e != hipSuccess) { (void)hipFree(d); return fail(MDK_ERR_NOMEM, "hipMalloc(reference codes)", e); }
     }
-    h->ref_carved[tid] = carved ? 1 : 0;
+    h->ref_carved[tid] = carved ? 1 : 0; h->refcap[tid] = carved ? std::max<int64_t>(h->refcap[tid], len + 16) : len + 16;
     // on a stream of its own: a contig can be uploaded (by another thread) while chunks of the contigs before it are worked on, and neither waits for the other
     if(!h->ref_stream && !(h->ref_stream = stream_take(h->device))) return fail(MDK_ERR_HIP, "hipStreamCreateWithFlags", hipGetLastError());
     HIPCHK(hipMemcpyAsync(d, seq, (size_t)len, hipMemcpyHostToDevice, h->ref_stream));
@@ -1304,7 +1369,7 @@ int launch_group_on(md_dev *h, const int *slots, int n, hipStream_t on, bool cro
         HIPCHK(hipGetLastError());
     }
     for(int i = 0; i < n; i++) get_slot(h, slots[i])->packed = false;
-    if(pack_wanted() && !on) {      // (not in the benchmarks' resident loops: their step is preparation + pileup) the ordered sites and the status blocks go to pinned host memory by a kernel of the same stream (k_sites_pack)
+    if(pack_wanted() && !on && !h->no_pack) {      // (not in the benchmarks' resident loops: their step is preparation + pileup) the ordered sites and the status blocks go to pinned host memory by a kernel of the same stream (k_sites_pack)
         KPack K; memset(&K, 0, sizeof(K)); K.n = n; bool ok = true;
         for(int i = 0; i < n && ok; i++) {
             Slot *s = get_slot(h, slots[i]);

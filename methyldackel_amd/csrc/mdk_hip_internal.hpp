@@ -128,14 +128,17 @@ struct Slot {
     bool busy = false;                 // work of this slot may still be running on its stream (uploaded or launched, results not collected yet): the next upload waits for the stream first
 };
 
+struct CallsState;                          // mdk_calls.hip
+MDK_HIDDEN void calls_state_free(md_dev *h);
 struct md_dev {
     int device; md_dev_cfg cfg; int tile, n_slots; bool variant; bool qw = false;
+    CallsState *calls = nullptr; bool no_pack = false;     // md_dev_calls_*: the compaction's state; no_pack: group launches leave their sites on the device
     std::vector<hipStream_t> streams;        // the streams the slots work on (cfg.n_streams of them, or one per slot)
     std::mutex crc_mu; void *d_crc = nullptr;   // constants of k_crc32 (mdk_inflate.hip), made by the first piece
     std::mutex piece_mu; std::vector<hipStream_t> piece_streams; int piece_rr = 0; hipStream_t piece_in = nullptr, piece_inf = nullptr;      /* the pieces' lanes (mdk_inflate.hip): the stream their compressed bytes cross the link on, the stream k_inflate runs on */      // the pieces' streams: a few, shared (mdk_inflate.hip piece_stream_of)
     hipStream_t ref_stream = nullptr;           // md_dev_set_reference works here, so that it neither waits for nor holds up the slots' streams    /* qw: dense contexts, a quarter of a wavefront per segment */
     std::vector<Slot> slots;
-    std::vector<char *> ref; std::vector<uint8_t *> refcode; std::vector<int64_t> reflen; std::vector<char> ref_carved;      /* ref_carved[tid]: the contig's two arrays came out of the carved blocks */
+    std::vector<char *> ref; std::vector<uint8_t *> refcode; std::vector<int64_t> reflen; std::vector<char> ref_carved; std::vector<int64_t> refcap;      /* ref_carved[tid]: the contig's two arrays came out of the carved blocks; refcap[tid]: their size in bytes */
     DBuf<SlotStatus> d_status; HBuf<SlotStatus> h_status;
     md_prep_cfg prep; bool prep_set = false; std::vector<uint32_t *> mapbits; std::vector<int64_t> maplen;
     std::vector<md_region *> d_runs; std::vector<int64_t> n_runs; std::vector<char> has_runs;       // -l runs kept for the read prefilter

@@ -29,7 +29,10 @@ static void load_dump(void) {
 }
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 typedef struct { double ready_at; int used, launched, handed_back; int32_t tid; int64_t beg, end; uint8_t *raw; uint64_t raw_bytes, raw_cap; uint32_t *off; uint32_t n_rec, off_cap; md_site *site; md_site_var *var; int64_t cap; } sslot;
-struct md_dev { md_dev_cfg cfg; int n_slots; sslot *slot; long n_up; int handback; pthread_mutex_t mu; double busy_until; int us_per_krec; };
+typedef struct { int32_t start, end, nm, nu; uint8_t ctx; int8_t strand; } crow_t;
+typedef struct { uint32_t key; int32_t tid; crow_t *row; int64_t n; } cchunk_t;
+struct md_dev { md_dev_cfg cfg; int n_slots; sslot *slot; long n_up; int handback; pthread_mutex_t mu; double busy_until; int us_per_krec;
+                md_calls_cfg ccfg; int calls_on; cchunk_t *cch; int n_cch, cap_cch; };
 const char *md_dev_last_error(void) { return t_err; }
 int md_dev_count(void) { return 1; }
 int md_dev_warm(int device) { (void)device; return 0; }
@@ -45,7 +48,8 @@ int md_dev_open(int device, const md_dev_cfg *cfg, md_dev **out) {
     h->us_per_krec = getenv("MDK_STANDIN_US_PER_KREC") ? atoi(getenv("MDK_STANDIN_US_PER_KREC")) : 0;
     *out = h; return h->slot ? 0 : MDK_ERR_NOMEM;
 }
-void md_dev_close(md_dev *h) { int i; if(!h) return; for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); } free(h->slot); free(h); }
+static void calls_drop(md_dev *h) { int i; for(i = 0; i < h->n_cch; i++) free(h->cch[i].row); free(h->cch); h->cch = NULL; h->n_cch = h->cap_cch = 0; h->calls_on = 0; }
+void md_dev_close(md_dev *h) { int i; if(!h) return; calls_drop(h); for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); } free(h->slot); free(h); }
 int md_dev_tile(const md_dev *h) { (void)h; return 2048; }
 int md_dev_reserve_contigs(md_dev *h, int32_t n) { (void)h; (void)n; return 0; }
 int md_dev_set_reference(md_dev *h, int32_t tid, const char *seq, int64_t len) { (void)h; (void)tid; (void)seq; (void)len; return 0; }
@@ -130,3 +134,100 @@ int md_dev_slot_sync(md_dev *h, int slot) { return slot_of(h, slot) ? 0 : MDK_ER
 int md_dev_sync(md_dev *h) { (void)h; return 0; }
 /* the exchange between GPUs is not stood in for: ranks that "share a device" use the command's TCP connections */
 int md_comm_unique_id(uint8_t *id) { (void)id; snprintf(t_err, sizeof t_err, "dev_standin: no RCCL"); return MDK_ERR_NODEVICE; }
+
+/* ---- calls on the "device": the rows k_calls_compact makes (csrc/mdk_calls.hip), restated over the slot's ascending sites ---- */
+struct md_calls_set { int64_t n; int32_t *contig, *start, *end, *nm, *nu; uint8_t *ctx; int8_t *strand; };
+int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
+    int i;
+    if(!h || !cfg || (cfg->n_slots > 0 ? cfg->n_slots : 2) != h->n_slots) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reset"); return MDK_ERR_ARG; }
+    calls_drop(h);
+    for(i = 0; i < h->n_slots; i++) { sslot *s = &h->slot[i]; s->used = s->launched = s->handed_back = 0; s->ready_at = 0; }
+    h->cfg = *cfg;
+    return 0;
+}
+int md_dev_calls_begin(md_dev *h, const md_calls_cfg *cfg) {
+    if(!h || !cfg || cfg->min_depth < 1) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_calls_begin"); return MDK_ERR_ARG; }
+    calls_drop(h); h->ccfg = *cfg; h->calls_on = 1;
+    return 0;
+}
+static int c_variant(const md_dev *h, const md_sites *s, int64_t i) {
+    return s->var && h->ccfg.min_opposite_depth > 0 && s->var[i].noff >= (uint32_t)h->ccfg.min_opposite_depth && (double)s->var[i].nvar / (double)s->var[i].noff >= h->ccfg.max_variant_frac;
+}
+static int64_t c_find(const md_sites *s, int64_t i, int dir, uint32_t pos, int type, int is_g) {      /* the site at `pos` within two of i, of that type and base */
+    int k;
+    for(k = 1; k <= 2; k++) { const int64_t j = i + dir * k; if(j < 0 || j >= s->n_sites) break; if(s->site[j].pos == pos && (int)(s->site[j].meta & 1) == is_g && (int)((s->site[j].meta >> 1) & 3) == type) return j; }
+    return -1;
+}
+static int chunk_rows(md_dev *h, const md_sites *s, cchunk_t *c) {
+    const md_calls_cfg *q = &h->ccfg; int64_t i;
+    c->row = malloc(sizeof(crow_t) * (size_t)(s->n_sites + 1)); c->n = 0;
+    if(!c->row) return MDK_ERR_NOMEM;
+    for(i = 0; i < s->n_sites; i++) {
+        const md_site *x = &s->site[i]; const int type = (x->meta >> 1) & 3, is_g = x->meta & 1;
+        const int surv = !c_variant(h, s, i) && x->nmeth + x->nunmeth > 0;
+        crow_t r; int has = 0; uint32_t m = 0, u = 0;
+        if(!q->ctx_on[type]) continue;
+        memset(&r, 0, sizeof(r)); r.ctx = (uint8_t)type;
+        if(!q->merge || type == 2) { if(surv) { has = 1; r.start = (int32_t)x->pos; r.end = r.start + 1; m = x->nmeth; u = x->nunmeth; r.strand = is_g ? -1 : 1; } }
+        else {
+            const int d = type + 1;
+            if(!is_g) {
+                const int64_t g = c_find(s, i, 1, x->pos + (uint32_t)d, type, 1);
+                const int vg = g >= 0 && c_variant(h, s, g), sg = g >= 0 && !vg && s->site[g].nmeth + s->site[g].nunmeth > 0;
+                if(surv || sg) {
+                    has = 1; r.start = (int32_t)x->pos; r.end = r.start + d + 1;
+                    m = (surv ? x->nmeth : 0) + (sg ? s->site[g].nmeth : 0); u = (surv ? x->nunmeth : 0) + (sg ? s->site[g].nunmeth : 0);
+                    if(surv && vg) m = u = 0;
+                }
+            } else if(surv && (x->pos < (uint32_t)d || c_find(s, i, -1, x->pos - (uint32_t)d, type, 0) < 0)) { has = 1; r.start = (int32_t)x->pos - d; r.end = (int32_t)x->pos + 1; m = x->nmeth; u = x->nunmeth; }
+        }
+        if(!has || m + u == 0 || m + u < (uint32_t)q->min_depth) continue;
+        r.nm = (int32_t)m; r.nu = (int32_t)u; c->row[c->n++] = r;
+    }
+    return 0;
+}
+int md_dev_calls_group(md_dev *h, const int *slots, const uint32_t *keys, int n, int *rc) {
+    int i;
+    if(!h || !slots || !keys || !rc || n < 1 || !h->calls_on) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_calls_group"); return MDK_ERR_ARG; }
+    for(i = 0; i < n; i++) {
+        md_sites st; cchunk_t c;
+        rc[i] = md_dev_download(h, slots[i], &st);
+        if(rc[i]) continue;
+        c.key = keys[i]; c.tid = h->slot[slots[i]].tid;
+        if((rc[i] = chunk_rows(h, &st, &c)) != 0) continue;
+        if(h->n_cch == h->cap_cch) { h->cap_cch = h->cap_cch ? 2 * h->cap_cch : 64; h->cch = realloc(h->cch, sizeof(cchunk_t) * (size_t)h->cap_cch); if(!h->cch) return MDK_ERR_NOMEM; }
+        h->cch[h->n_cch++] = c;
+    }
+    return 0;
+}
+static int cchunk_cmp(const void *a, const void *b) { const cchunk_t *x = a, *y = b; return x->key < y->key ? -1 : x->key > y->key; }
+int md_dev_calls_finish(md_dev *h, md_calls_set **out) {
+    md_calls_set *r; int64_t n = 0, o = 0; int i, k;
+    if(!h || !out || !h->calls_on) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_calls_finish"); return MDK_ERR_ARG; }
+    qsort(h->cch, (size_t)h->n_cch, sizeof(cchunk_t), cchunk_cmp);
+    for(i = 0; i < h->n_cch; i++) n += h->cch[i].n;
+    r = calloc(1, sizeof(*r)); if(!r) return MDK_ERR_NOMEM;
+    r->n = n; r->contig = malloc(4 * (size_t)(n + 1)); r->start = malloc(4 * (size_t)(n + 1)); r->end = malloc(4 * (size_t)(n + 1)); r->nm = malloc(4 * (size_t)(n + 1)); r->nu = malloc(4 * (size_t)(n + 1));
+    r->ctx = malloc((size_t)n + 1); r->strand = malloc((size_t)n + 1);
+    for(i = 0; i < h->n_cch; i++) for(k = 0; k < h->cch[i].n; k++, o++) {
+        const crow_t *x = &h->cch[i].row[k];
+        r->contig[o] = h->cch[i].tid; r->start[o] = x->start; r->end[o] = x->end; r->nm[o] = x->nm; r->nu[o] = x->nu; r->ctx[o] = x->ctx; r->strand[o] = x->strand;
+    }
+    calls_drop(h);
+    *out = r;
+    return 0;
+}
+int64_t md_calls_set_count(const md_calls_set *c) { return c ? c->n : MDK_ERR_ARG; }
+int md_calls_set_copy(const md_calls_set *c, const md_calls_cols *d, int to_host) {
+    const size_t n = c ? (size_t)c->n : 0; (void)to_host;      /* ("device" memory is host memory here) */
+    if(!c || !d) return MDK_ERR_ARG;
+    if(d->contig) memcpy(d->contig, c->contig, 4 * n);
+    if(d->start) memcpy(d->start, c->start, 4 * n);
+    if(d->end) memcpy(d->end, c->end, 4 * n);
+    if(d->nmeth) memcpy(d->nmeth, c->nm, 4 * n);
+    if(d->nunmeth) memcpy(d->nunmeth, c->nu, 4 * n);
+    if(d->context) memcpy(d->context, c->ctx, n);
+    if(d->strand) memcpy(d->strand, c->strand, n);
+    return 0;
+}
+void md_calls_set_free(md_calls_set *c) { if(!c) return; free(c->contig); free(c->start); free(c->end); free(c->nm); free(c->nu); free(c->ctx); free(c->strand); free(c); }
