@@ -4,13 +4,18 @@
   * command level: `MethylDackel extract` with every piece but the header's inflated on the device (MDK_DEVICE_INFLATE_ONLY=1)
     must produce the oracle's bytes, over chunk sizes far below a member's span (a member then serves many chunks), regions
     through the index, dense contexts, --mergeContext, a file whose records straddle BGZF members (read back to the host) and a
-    chunk the device preparation hands back to the host (its records exist only on the device)."""
+    chunk the device preparation hands back to the host (its records exist only on the device);
+  * the deflate stream zoo (tests/deflate_zoo.py: every zlib level / strategy / memLevel / window, flushes, libdeflate, hand-written blocks)
+    as pieces against zlib, k_crc32 at every length edge and alignment with one CRC bit flipped at a time, malformed members refused with
+    the emulator's error code, and BAMs re-encoded by other encoders through the command against the oracle."""
 import ctypes as C
 import struct
+import warnings
 import zlib
 
 import pytest
 
+import deflate_zoo as Z
 import methyldackel_amd as mdk
 from conftest import REPO, synth
 from test_gpu_parity import compare_cli
@@ -259,3 +264,245 @@ def test_a_byte_flipped_inside_a_stored_block_fails_the_crc32_check(tmp_path):
         assert r.returncode != 0 and "CRC32" in r.stderr, (name, r.returncode, r.stderr[-800:])
         r = mdk.run_cli([str(tmp_path / "s.fa"), str(tmp_path / "bad.bam"), "-o", "out"], cwd=d, env=dict(env, MDK_NO_CRC="1"))
         assert r.returncode == 0, (name, "without the check the damage goes unnoticed", r.stderr[-800:])
+
+
+# ---- the deflate stream zoo (tests/deflate_zoo.py) through the C ABI: every stream kind the encoders write, against zlib ----
+EMU = REPO / "tools" / "_build" / "inflate_emu"
+
+
+@pytest.fixture(scope="module")
+def zoo():
+    return Z.build_zoo()
+
+
+class PieceRig:
+    """one device handle and one piece, reused by every submit (buffers grown on demand, then used again at other offsets)"""
+
+    def __init__(self):
+        self.L = mdk.lib_hip()
+        self.L.md_host_alloc.restype = C.c_void_p
+        cfg = mdk.md_dev_cfg(); cfg.keepCpG = 1; cfg.minPhred = 5
+        self.dev = mdk.Device(cfg)
+        self.piece = C.c_void_p()
+        assert self.L.md_piece_create(self.dev.h, C.byref(self.piece)) == 0, self.L.md_dev_last_error()
+        self.stage, self.cap = None, 0
+
+    def submit(self, items, seed=1):
+        """items: [(stream, out_len, crc)] -> (rc of md_piece_wait, error text, info, member table)"""
+        comp, tab = Z.piece_layout(items, seed)
+        if len(comp) + 64 > self.cap:
+            if self.stage:
+                self.L.md_host_free(C.c_void_p(self.stage))
+            self.cap = len(comp) + 64 + (1 << 20)
+            self.stage = self.L.md_host_alloc(C.c_uint64(self.cap))
+        C.memmove(self.stage, comp, len(comp))
+        mt = (mdk.md_inf_member * len(tab))()
+        for i, (io, il, ol, oo, c) in enumerate(tab):
+            mt[i].in_off, mt[i].in_len, mt[i].out_len, mt[i].out_off, mt[i].crc32 = io, il, ol, oo, c
+        assert self.L.md_piece_submit(self.piece, C.c_void_p(self.stage), len(comp), mt, len(tab)) == 0, self.L.md_dev_last_error()
+        info = mdk.md_piece_info()
+        rc = self.L.md_piece_wait(self.piece, C.byref(info))
+        return rc, (self.L.md_dev_last_error() or b"").decode(), info, tab
+
+    def read(self, tab):
+        n = tab[-1][3] + tab[-1][2]
+        got = C.create_string_buffer(max(1, n))
+        assert self.L.md_piece_read(self.piece, 0, n, got) == 0
+        return got.raw[:n]
+
+    def close(self):
+        self.L.md_piece_destroy(self.piece)
+        if self.stage:
+            self.L.md_host_free(C.c_void_p(self.stage))
+        self.dev.close()
+
+
+@pytest.fixture(scope="module")
+def rig():
+    r = PieceRig()
+    yield r
+    r.close()
+
+
+def check_piece(rig, members, seed=1):
+    """members: [Member] submitted as one piece with right CRCs: every member's bytes equal zlib's; BAM payload members' digests equal walk()'s"""
+    rc, err, info, tab = rig.submit([(m.stream, len(m.raw), zlib.crc32(m.raw)) for m in members], seed)
+    assert rc == 0, err
+    assert info.n_mem == len(members) and info.out_bytes == tab[-1][3] + tab[-1][2] == sum(len(m.raw) for m in members)
+    got = rig.read(tab)
+    recs = (C.c_uint32 * max(1, info.n_records))()
+    assert rig.L.md_piece_read_records(rig.piece, 0, info.n_records, recs) == 0
+    first, n_bam = 0, 0
+    for i, m in enumerate(members):
+        oo = tab[i][3]
+        assert got[oo:oo + len(m.raw)] == m.raw == zlib.decompress(m.stream, -15), (i, m.name)
+        g = info.digest[i]
+        assert g.first_rec == first, (i, m.name)
+        if "bam" in m.name:
+            offs, dg = walk(m.raw)
+            assert g.ok == 1 and (g.n_rec, g.tid0, g.pos0, g.tidN, g.posN, g.min_endp, g.max_endp, g.sorted) == dg, m.name
+            assert [recs[first + k] for k in range(len(offs))] == [oo + x for x in offs], m.name
+            n_bam += 1
+        first += g.n_rec
+    assert first == info.n_records
+    return n_bam
+
+
+def test_piece_zoo_equals_zlib(rig, zoo):
+    """the whole zoo as one piece; again reversed on the same piece (its buffers reused at other offsets); libdeflate's members with it,
+    or a warning that names them as left out"""
+    if not Z.libdeflate():
+        warnings.warn("libdeflate.so.0 is not on this machine: the zoo's libdeflate members are left out of the piece")
+    else:
+        assert sum(m.name.startswith("libdeflate") for m in zoo) == 28
+    assert check_piece(rig, zoo) >= 5
+    assert check_piece(rig, zoo[::-1], seed=2) >= 5
+
+
+def test_pieces_of_one_round_and_one_more(rig, zoo):
+    """exactly the members k_inflate keeps resident at once, and one more (a second round of one member)"""
+    n = rig.L.md_piece_members_per_round(rig.dev.h)
+    assert n > 0
+    for k in (n, n + 1):
+        check_piece(rig, [zoo[(7 * i) % len(zoo)] for i in range(k)], seed=k)
+
+
+CRC_LENGTHS = list(range(1, 66)) + [0, 1007, 1008, 1009, 1023, 1024, 1025, 16127, 16128, 16129, 65279, 65280, 65535, 65536]
+
+
+def crc_items():
+    """zero / 0xFF / random members of CRC_LENGTHS; the long ones at every out_off % 16 (a short member in front sets the offset)"""
+    import random
+    rnd = random.Random(11)
+    raw = []
+    for L in CRC_LENGTHS:
+        for kind in ("zero", "ff", "random"):
+            raw.append(Z.content(kind, L, rnd))
+    at = sum(map(len, raw))
+    for L in CRC_LENGTHS[66:]:
+        for r in range(16):
+            pad = (r - at) % 16
+            if pad:
+                raw.append(rnd.randbytes(pad)); at += pad
+            raw.append(Z.content(("zero", "ff", "random")[r % 3], L, rnd)); at += L
+    return [(Z.zraw(d, 1), len(d), zlib.crc32(d)) for d in raw]
+
+
+def test_crc32_every_length_edge_and_alignment(rig):
+    items = crc_items()
+    _, tab = Z.piece_layout(items)
+    assert {t[3] % 16 for t in tab if t[2] >= 1007} == set(range(16))
+    rc, err, info, tab = rig.submit(items)
+    assert rc == 0, err
+    # one flipped CRC bit at a time: first, middle and last member, short and long members
+    lens = [n for _, n, _ in items]
+    picks = [0, 1, 2, 5, 64, 100, 150, 194, len(items) // 2, len(items) - 1]
+    for L in (1007, 1008, 1024, 16128, 16129, 65279, 65536):
+        picks.append(lens.index(L))
+    seen = set()
+    for k, i in enumerate(picks):
+        if i in seen or lens[i] == 0:
+            continue
+        seen.add(i)
+        bad = list(items); s, n, c = bad[i]; bad[i] = (s, n, c ^ (1 << (k % 32)))
+        rc, err, _, _ = rig.submit(bad)
+        assert rc != 0 and "CRC32" in err and f"member {i} of the piece" in err, (i, n, err)
+    assert len(seen) >= 16 and 0 in seen and len(items) - 1 in seen
+    # a member of no bytes with a CRC that is not 0
+    z = lens.index(0)
+    bad = list(items); bad[z] = (items[z][0], 0, 0x1234)
+    rc, err, _, _ = rig.submit(bad)
+    assert rc != 0 and f"member {z} of the piece" in err, err
+    rc, err, _, _ = rig.submit(items)
+    assert rc == 0, err
+
+
+def test_malformed_members_are_refused_and_the_piece_recovers(rig, zoo, tmp_path):
+    """ISIZE one off, streams cut short, a distance behind byte 0: refused naming the member, with the error code the shared decoder gives
+    (tools/inflate_emu --each on the same members); the good members on either side of it in the same launch (Z.AROUND_MALFORMED: far
+    matches, stored blocks, pass-capped batches, none empty) are byte-exact all the same, and so is the next submit on the same piece"""
+    import json
+    import re
+    import subprocess
+    good = Z.around_malformed(zoo)
+    gi = [(m.stream, len(m.raw), zlib.crc32(m.raw)) for m in good]
+    assert all(n >= 1000 for _, n, _ in gi) and sum(n for _, n, _ in gi) > 200000
+    bad = Z.malformed()
+    f = tmp_path / "bad.bam"
+    f.write_bytes(Z.bgzf_file([(s, n, 0) for _, s, n in bad]))
+    r = subprocess.run([str(EMU), "--each", str(f)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    want = json.loads(r.stdout)["rc"]
+    for k, (name, s, n) in enumerate(bad):
+        assert want[k] > 0, name
+        rc, err, _, tab = rig.submit(gi[:3] + [(s, n, 0)] + gi[3:], seed=k)
+        m = re.search(r"error (\d+) in member (\d+) of the piece", err)
+        assert rc != 0 and m and int(m.group(2)) == 3, (name, err)
+        # (a stream cut short is read on into the bytes behind it, which differ between the emulator's file and the piece: any refusal)
+        assert int(m.group(1)) == want[k] if "cut" not in name else 0 < int(m.group(1)) < 12, (name, want[k], err)
+        got = rig.read(tab)
+        for i, g in zip((0, 1, 2, 4, 5, 6), good):
+            assert got[tab[i][3]:tab[i][3] + tab[i][2]] == g.raw, (name, "good member", i, g.name)
+        assert check_piece(rig, good, seed=k + 100) == 1
+
+
+# ---- command level: a BAM re-encoded the way other writers encode it ----
+@pytest.fixture(scope="module")
+def reenc(tmp_path_factory):
+    d = tmp_path_factory.mktemp("reenc")
+    synth(d / "s", "-L", "1500000", "-c", "25", "-s", "41", "--extras")
+    hdr, recs = Z.bam_split((d / "s.bam").read_bytes())
+    return d, hdr, recs
+
+
+def _z(level, strategy=zlib.Z_DEFAULT_STRATEGY, memlevel=8):
+    return lambda data: Z.zraw(data, level, strategy, -15, memlevel)
+
+
+REENC = {"zlib0": (_z(0), 65280), "zlib1": (_z(1), 65280), "zlib6": (_z(6), 65280), "zlib9": (_z(9), 65280), "filtered": (_z(6, zlib.Z_FILTERED), 65280),
+         "huffman_only": (_z(6, zlib.Z_HUFFMAN_ONLY), 65280), "rle": (_z(6, zlib.Z_RLE), 65280), "fixed": (_z(6, zlib.Z_FIXED), 65280),
+         "zlib9_memlevel1": (_z(9, memlevel=1), 65280), "sync_every_record": (None, 65280), "small_members": (_z(6), 5000), "members_65536": (_z(6), 65536),
+         "libdeflate1": ("ld", 1), "libdeflate6": ("ld", 6), "libdeflate12": ("ld", 12)}
+
+
+def device_pieces(stderr):
+    line = [l for l in stderr.splitlines() if "on the device" in l]
+    assert line, stderr[-2000:]
+    return int(line[0].split("on the device ")[1].split()[0])
+
+
+@pytest.mark.parametrize("variant", list(REENC))
+def test_cli_reencoded_bam_equals_oracle(reenc, tmp_path, variant):
+    d, hdr, recs = reenc
+    enc, lim = REENC[variant]
+    if enc == "ld":
+        if not Z.libdeflate():
+            pytest.skip("libdeflate.so.0 is not on this machine")
+        enc, lim = (lambda data, lv=lim: Z.ldraw(data, lv)), 65280
+    (tmp_path / "v.bam").write_bytes(Z.bam_reencode(hdr, recs, enc, lim, sync=variant == "sync_every_record"))
+    compare_cli(tmp_path, [str(d / "s.fa"), str(tmp_path / "v.bam")], env=DEV)
+    assert device_pieces((tmp_path / "gpu_stderr.txt").read_text()) >= 1
+
+
+@pytest.mark.parametrize("damage", ["truncated_member", "isize_plus_1"])
+def test_cli_damaged_member_is_refused_by_every_path(reenc, tmp_path, damage):
+    """a member in the middle of the file cut short by two bytes (BSIZE says so), or its ISIZE one too large: the device's inflate, the host's
+    and the oracle (htslib's bgzf_read_block: inflate error / "Inflated block size mismatch") all stop, each product path with its own
+    refusal of the member (csrc/mdk_inflate.hip md_piece_wait, csrc/host/mdk_io.c inflate_worker)"""
+    from conftest import run_oracle
+    d, hdr, recs = reenc
+    raw = Z.bam_reencode(hdr, recs, _z(6), 65280)
+    mem = Z.bgzf_members(raw)
+    k = len(mem) // 2
+    io, il, isz, crc = mem[k]
+    s = raw[io:io + il]
+    if damage == "truncated_member":
+        s = s[:-2]
+    bad = raw[:io - 18] + Z.bgzf_member(s, isz + (damage == "isize_plus_1"), crc) + raw[io + il + 8:]
+    (tmp_path / "bad.bam").write_bytes(bad)
+    (tmp_path / "o").mkdir()
+    assert run_oracle([str(d / "s.fa"), str(tmp_path / "bad.bam"), "-o", "out"], cwd=tmp_path / "o").returncode != 0
+    for name, env, says in (("device", DEV, "BGZF inflate failed on the device"), ("host", {"MDK_HOST_INFLATE": "1"}, "BGZF inflate failed (corrupt file?)")):
+        w = tmp_path / name; w.mkdir()
+        r = mdk.run_cli([str(d / "s.fa"), str(tmp_path / "bad.bam"), "-o", "out"], cwd=w, env=env)
+        assert r.returncode != 0 and says in r.stderr, (name, r.returncode, r.stderr[-800:])

@@ -4,7 +4,8 @@
 // re-stated here with the same per-lane bodies and the kernel's barriers turned into loop boundaries.
 //   build: g++ -O2 -o tools/_build/inflate_emu tools/inflate_emu.cpp -Imethyldackel_amd/csrc -lz
 //   run:   inflate_emu file.bam [max_members]      (exit 0 = every member identical to zlib)
-// Also: inflate_emu --fuzz N runs N damaged streams (see fuzz()); inflate_emu --selftest  runs deflate streams made with zlib at every level/strategy (stored, fixed, dynamic blocks,
+// Also: inflate_emu --each file.bam prints the verdict on every member, legal or not (each_member());
+// inflate_emu --fuzz N runs N damaged streams (see fuzz()); inflate_emu --selftest  runs deflate streams made with zlib at every level/strategy (stored, fixed, dynamic blocks,
 // long matches, distance-1 runs, maximum-distance matches, empty input).
 #include <stdint.h>
 #include <stdio.h>
@@ -271,8 +272,38 @@ static int crctest(long n) {
     return bad ? 1 : 0;
 }
 
+// Every member of a BGZF file as it stands, legal or not (ISIZE wrong, stream cut short, a distance behind byte 0): the decoder's verdict per
+// member, -1 where it accepted a member whose bytes zlib does not give back.  The tests send the same members to the GPU and expect the same verdicts.
+static int each_member(const std::vector<uint8_t> &raw, size_t n) {
+    size_t o = 0; long m = 0; std::vector<uint8_t> ref(65536 + 64), got(65536 + 64);
+    printf("{\"rc\": [");
+    while(o + 18 <= n) {
+        const uint16_t xlen = (uint16_t)(raw[o + 10] | raw[o + 11] << 8); const uint32_t bs = (uint32_t)(raw[o + 16] | raw[o + 17] << 8) + 1; uint32_t isz; memcpy(&isz, &raw[o + bs - 4], 4);
+        const uint64_t in_off = o + 12 + xlen; const uint32_t in_len = bs - 12 - xlen - 8;
+        if(isz > 65536) { fprintf(stderr, "member %ld: ISIZE %u\n", m, isz); return 2; }
+        memset(got.data(), 0xEE, got.size()); uint64_t c = 0;
+        int rc = emu_member(raw.data(), in_off, in_len, got.data(), isz, &c);
+        for(size_t i = isz; i < got.size(); i++) if(got[i] != 0xEE) { rc = -2; break; }       // a byte beyond the announced size
+        if(rc == 0 && isz) {
+            z_stream zs; memset(&zs, 0, sizeof zs); zs.next_in = (Bytef *)raw.data() + in_off; zs.avail_in = in_len; zs.next_out = ref.data(); zs.avail_out = isz;
+            inflateInit2(&zs, -15); const int zr = inflate(&zs, Z_FINISH); const size_t zout = zs.total_out; inflateEnd(&zs);
+            if(zr != Z_STREAM_END || zout != isz || memcmp(ref.data(), got.data(), isz)) rc = -1;
+        }
+        printf("%s%d", m ? ", " : "", rc);
+        o += bs; m++;
+    }
+    printf("], \"members\": %ld}\n", m);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if(argc > 1 && !strcmp(argv[1], "--selftest")) return selftest();
+    if(argc > 2 && !strcmp(argv[1], "--each")) {
+        FILE *f = fopen(argv[2], "rb"); if(!f) { perror(argv[2]); return 2; }
+        fseek(f, 0, SEEK_END); size_t n = (size_t)ftell(f); fseek(f, 0, SEEK_SET);
+        std::vector<uint8_t> raw(n + 64, 0); if(fread(raw.data(), 1, n, f) != n) return 2; fclose(f);
+        return each_member(raw, n);
+    }
     if(argc > 2 && !strcmp(argv[1], "--crc")) return crctest(atol(argv[2]));
     if(argc > 2 && !strcmp(argv[1], "--fuzz")) return fuzz(atol(argv[2]));
     if(argc < 2) { fprintf(stderr, "usage: inflate_emu file.bam [max_members] | --selftest\n"); return 2; }
