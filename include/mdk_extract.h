@@ -159,6 +159,30 @@ const char *mdk_calls_contig_name(const mdk_calls *c, int i);
 int  mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host);
 void mdk_calls_free(mdk_calls *c);
 
+/* ---- the same session's perRead: per-read methylation as device-resident columns ----
+ * mdk_session_perread takes the argv of perRead_main (argv[0] = "perRead"), parses it with the same code and returns the same codes for the
+ * same errors.  Instead of text it returns one row per line the command would print, in the same order (chunks in schedule order, reads
+ * within a chunk in file order) -- include/mdk_hip.h "reads on the device":
+ *   contig (int32, BAM header index), pos (int32, the line's column 3), nmeth, nunmeth (int32: the line prints 100*nmeth/(nmeth+nunmeth)
+ *   and the sum), name_offsets (int64, count + 1 entries, the first 0) and name_bytes (uint8: the names back to back, each what %s prints
+ *   of the record's name).
+ * Differences from the command: -o is ignored and nothing is opened for writing; the process is never left through _exit.  -h / --version
+ * return 0 and an empty mdk_reads (no device memory: its one name offset, 0, can be copied to the host only).  A run uses the device handle
+ * with the slots and streams of an extract run, so extract and perRead runs alternate on one handle (md_dev_reset between runs).
+ * Ownership and lifetimes are those of mdk_calls: each successful mdk_session_perread returns a new mdk_reads (*out; NULL on error) that owns
+ * its rows in device memory and its contig names, does not depend on the session and stays valid, also after mdk_session_close, until
+ * mdk_reads_free.  mdk_reads_copy is synchronous: `dst` (device memory of the session's device when to_host = 0, host memory when 1) holds
+ * the column when it returns -- mdk_reads_count entries, count + 1 for MDK_READS_NAME_OFFSETS, mdk_reads_name_bytes for MDK_READS_NAME_BYTES. */
+typedef struct mdk_reads mdk_reads;
+enum { MDK_READS_CONTIG = 0, MDK_READS_POS, MDK_READS_NMETH, MDK_READS_NUNMETH, MDK_READS_NAME_OFFSETS, MDK_READS_NAME_BYTES };   /* int32 x4, int64, uint8 */
+int  mdk_session_perread(mdk_session *s, int argc, char *argv[], mdk_reads **out);
+int64_t mdk_reads_count(const mdk_reads *r);
+int64_t mdk_reads_name_bytes(const mdk_reads *r);
+int  mdk_reads_n_contigs(const mdk_reads *r);
+const char *mdk_reads_contig_name(const mdk_reads *r, int i);
+int  mdk_reads_copy(const mdk_reads *r, int column, void *dst, int to_host);
+void mdk_reads_free(mdk_reads *r);
+
 /* ---- `mergeContext` (mergeContext.c; main.c:19,53-54): text-to-text host tool, no device work ---- */
 int  mergeContext_main(int argc, char *argv[]);
 

@@ -364,8 +364,42 @@ int64_t md_calls_set_count(const md_calls_set *c);
 /* synchronous copies of the columns into DEVICE memory of the set's device (to_host = 0) or host memory (to_host = 1) */
 int  md_calls_set_copy(const md_calls_set *c, const md_calls_cols *dst, int to_host);
 void md_calls_set_free(md_calls_set *c);
+
+/* ---- reads on the device (a resident perRead session: include/mdk_extract.h mdk_session_perread) ----
+ * The rows `perRead` prints (addRead, perRead.c:16-36), kept as columns instead of text:
+ *   contig (int32) the chunk's tid; pos (int32) the record's pos; nmeth, nunmeth (int32) the read's CpG calls;
+ *   name_off (int64, n + 1 entries, the first 0) and name bytes (uint8): the read names back to back, each the record's l_read_name
+ *   bytes up to the first NUL (what %s prints).
+ * Rows come in the order of the calls below, which the caller makes in schedule order; within a device-selected chunk, the kept reads
+ * in file order.
+ * Sequence: md_dev_reads_begin; then per chunk either
+ *   - md_dev_perread_submit_raw + md_dev_reads_slot (queued on the slot's stream behind k_perread_raw, no host wait), later
+ *     md_dev_reads_collect, which waits for the slot and appends its rows.  Between begin and finish md_dev_perread_submit_raw copies
+ *     nothing of the reads back (md_dev_perread_download_raw must not be used); or
+ *   - md_dev_reads_host for a chunk whose reads the host listed (counts NULL: all zero);
+ * then md_dev_reads_finish.  Single caller thread for the reads_* functions of a handle.
+ * Ownership: the handle keeps a row arena and per-slot staging in device memory (grown by doubling, kept until md_dev_reset /
+ * md_dev_close); md_dev_reads_finish returns a md_reads_set that owns its device memory at its exact size, independent of the handle
+ * (it may outlive it), until md_reads_set_free. */
+typedef struct md_reads_set md_reads_set;
+/* destination of md_reads_set_copy: n entries each (name_off: n + 1, name_bytes: md_reads_set_name_bytes); a NULL column is not copied */
+typedef struct { int32_t *contig, *pos, *nmeth, *nunmeth; int64_t *name_off; uint8_t *name_bytes; } md_reads_cols;
+int  md_dev_reads_begin(md_dev *h);
+/* after md_dev_perread_submit_raw on `slot`: the kept reads' name lengths and their scan, queued on the slot's stream */
+int  md_dev_reads_slot(md_dev *h, int slot);
+/* waits for the slot; appends its rows (its kept reads, their counts and names) to the run's rows; *n: how many.  Returns what
+ * md_dev_perread_download_raw would have returned (MDK_ERR_ARG for a malformed record: nothing is appended then). */
+int  md_dev_reads_collect(md_dev *h, int slot, int64_t *n);
+/* n reads of contig tid listed by the host: pos[i], counts[i] (NULL: no calls), name i = names[name_off[i] .. name_off[i + 1]) */
+int  md_dev_reads_host(md_dev *h, int32_t tid, int64_t n, const int32_t *pos, const md_pr_count *counts, const uint64_t *name_off, const uint8_t *names);
+int  md_dev_reads_finish(md_dev *h, md_reads_set **out);
+int64_t md_reads_set_count(const md_reads_set *r);
+int64_t md_reads_set_name_bytes(const md_reads_set *r);
+/* synchronous copies of the columns into DEVICE memory of the set's device (to_host = 0) or host memory (to_host = 1) */
+int  md_reads_set_copy(const md_reads_set *r, const md_reads_cols *dst, int to_host);
+void md_reads_set_free(md_reads_set *r);
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
- * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram and the calls state
+ * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram, the calls and reads state
  * are dropped, every slot's buffers are given back.  Pointers the library returned for the handle before (md_sites, md_sites_dev,
  * md_mbias) are void afterwards; md_piece objects must have been destroyed first.  When no other handle is open, the carved device
  * memory is reused from its start (a handle used for run after run would otherwise keep taking more). */

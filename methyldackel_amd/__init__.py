@@ -166,14 +166,16 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_mbias_submit", "md_dev_mbias_submit_raw", "md_dev_mbias_read", "md_dev_mbias_reset", "md_dev_slot_sync",
                "md_dev_perread_submit", "md_dev_perread_download", "md_dev_perread_submit_raw", "md_dev_perread_download_raw", "md_dev_read_raw",
                "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
-               "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset"]
+               "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
+               "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
                    "mdk_plan_host_prepare_from", "mdk_plan_release_records", "mdk_plan_attach_device", "mdk_plan_detach_device",
                    "mbias_main", "mdk_cli_quiesce", "mdk_plan_open_mbias", "mdk_plan_mbias_outputs", "mdk_mbias_report",
                    "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node",
-                   "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free"]
+                   "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free",
+                   "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free"]
 
 _hip = None
 _ext = None
@@ -643,6 +645,16 @@ def _session_lib():
         L.mdk_calls_contig_name.restype = C.c_char_p
         L.mdk_calls_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.mdk_calls_free.argtypes = [C.c_void_p]
+        L.mdk_session_perread.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+        L.mdk_reads_count.argtypes = [C.c_void_p]
+        L.mdk_reads_count.restype = C.c_int64
+        L.mdk_reads_name_bytes.argtypes = [C.c_void_p]
+        L.mdk_reads_name_bytes.restype = C.c_int64
+        L.mdk_reads_n_contigs.argtypes = [C.c_void_p]
+        L.mdk_reads_contig_name.argtypes = [C.c_void_p, C.c_int]
+        L.mdk_reads_contig_name.restype = C.c_char_p
+        L.mdk_reads_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.mdk_reads_free.argtypes = [C.c_void_p]
         L._session_types = True
     return L
 
@@ -666,12 +678,41 @@ class Calls:
         return [(self.contigs[c], a, b, m, u) for c, a, b, m, u, x in zip(*cols) if context is None or x == context]
 
 
+READ_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("name_offsets", "int64"), ("name_bytes", "uint8"))
+
+
+class Reads:
+    """The lines `perRead` would print, as columns (one row per line, in the command's order: chunks of the schedule, reads of a chunk in
+    file order): ``contig`` (int32, index into ``contigs``), ``pos`` (int32, the line's column 3), ``nmeth``/``nunmeth`` (int32: the line
+    prints 100*nmeth/(nmeth+nunmeth) and the sum), ``name_offsets`` (int64, len + 1 entries, the first 0) and ``name_bytes`` (uint8, the read
+    names packed without separators: name i is name_bytes[name_offsets[i]:name_offsets[i + 1]])."""
+
+    def __init__(self, contigs, columns):
+        self.contigs = contigs
+        for name, _ in READ_COLUMNS:
+            setattr(self, name, columns[name])
+
+    def __len__(self):
+        return int(self.pos.shape[0])
+
+    def names(self):
+        """the read names on the host, as str"""
+        off, b = self.name_offsets.cpu().tolist(), self.name_bytes.cpu().numpy().tobytes()
+        return [b[off[i]:off[i + 1]].decode("latin-1") for i in range(len(self))]
+
+    def rows(self):
+        """(name, chrom, pos, nmeth, nunmeth) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n in ("contig", "pos", "nmeth", "nunmeth")]
+        return [(q, self.contigs[c], p, m, u) for q, c, p, m, u in zip(self.names(), *cols)]
+
+
 class Session:
     """One process, one device handle, many `extract` runs: ``Session(device=0).extract(args) -> Calls``.  ``args`` is the extract
     command line as for run_cli (without the command name).  The rows never pass through text: they are compacted on the device
     (k_calls_compact) and copied device to device into tensors torch allocated on ``torch.device("cuda", device)``; with
     ``device_tensors=False`` into CPU tensors instead.  --fraction/--counts/--logit/--methylKit/--cytosine_report are refused (rc -23),
-    -o is ignored; any non-zero return code raises MdkError with ``.rc``."""
+    -o is ignored; any non-zero return code raises MdkError with ``.rc``.  ``perread(args) -> Reads`` runs `perRead` command lines on the
+    same handle."""
 
     def __init__(self, device: int = 0):
         self.device = device
@@ -707,6 +748,35 @@ class Session:
         finally:
             self._L.mdk_calls_free(out)
         return Calls(contigs, cols)
+
+    def perread(self, args, device_tensors: bool = True) -> Reads:
+        """The `perRead` command line (without the command name) on the same handle: the rows it would print, as Reads.  -o is ignored;
+        any non-zero return code raises MdkError with ``.rc``.  Extract and perRead runs may alternate on one session."""
+        import torch
+        if self._h is None:
+            raise MdkError("the session is closed")
+        argv = ["perRead"] + [str(a) for a in args]
+        arr = (C.c_char_p * (len(argv) + 1))(*[os.fsencode(a) for a in argv], None)
+        out = C.c_void_p()
+        rc = self._L.mdk_session_perread(self._h, len(argv), arr, C.byref(out))
+        if rc:
+            raise _rc_error("perRead", rc)
+        try:
+            n, nb = int(self._L.mdk_reads_count(out)), int(self._L.mdk_reads_name_bytes(out))
+            contigs = [self._L.mdk_reads_contig_name(out, i).decode() for i in range(self._L.mdk_reads_n_contigs(out))]
+            dev = torch.device("cuda", self.device) if device_tensors else torch.device("cpu")
+            cols = {}
+            for k, (name, dt) in enumerate(READ_COLUMNS):
+                size = n + 1 if name == "name_offsets" else nb if name == "name_bytes" else n
+                t = torch.zeros(size, dtype=getattr(torch, dt), device=dev) if n == 0 else torch.empty(size, dtype=getattr(torch, dt), device=dev)
+                if n and size:
+                    rc = self._L.mdk_reads_copy(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
+                    if rc:
+                        raise _rc_error(f"copying the {name} column", rc)
+                cols[name] = t
+        finally:
+            self._L.mdk_reads_free(out)
+        return Reads(contigs, cols)
 
     def close(self):
         if self._h is not None:

@@ -13,7 +13,8 @@ static void perread_usage(void) {
 " -R/--requireFlags INT, -@ INT, --chunkSize INT, --version\n", stderr);
 }
 
-int mdk_plan_open_perread(int argc, char *argv[], mdk_plan **out) {
+/* session = 1: a session's command line -- -o is ignored and nothing is opened for writing */
+static int perread_open(int argc, char *argv[], mdk_plan **out, int session) {
     static const struct option longopts[] = {            /* perRead.c:300-308; --ignoreNH is in the help text only */
         {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"chunkSize", required_argument, 0, 19}, {"keepStrand", no_argument, 0, 20},
         {"ignoreFlags", required_argument, 0, 'F'}, {"requireFlags", required_argument, 0, 'R'}, {0, 0, 0, 0}};
@@ -26,12 +27,13 @@ int mdk_plan_open_perread(int argc, char *argv[], mdk_plan **out) {
     p->shard_rank = 0; p->shard_world = 1;
     p->last_tid = -1; p->last_pos = -1; p->carry_tid = -1;
     p->pr_out = stdout;
-    optind = 1;
+    optind = 0;          /* (glibc: a full reset -- a parse that stopped early, at -h, leaves getopt pointing into the argv of that call) */
     while((c = getopt_long(argc, argv, "hvq:p:o:@:r:l:F:R:", longopts, NULL)) >= 0) {
         switch(c) {
         case 'h': perread_usage(); plan_free(p); return 0;
         case 'v': printf("%s (using HTSlib version %s)\n", MDK_VERSION, "none; methyldackel_amd MI355X build"); plan_free(p); return 0;
         case 'o':
+            if(session) break;
             if(p->pr_out_owned) fclose(p->pr_out);
             if((p->pr_out = fopen(optarg, "w")) == NULL) { fprintf(stderr, "Couldn't open %s for writing\n", optarg); p->pr_out_owned = 0; plan_free(p); return 2; }
             p->pr_out_owned = 1;
@@ -58,6 +60,8 @@ int mdk_plan_open_perread(int argc, char *argv[], mdk_plan **out) {
     *out = p;
     return 0;
 }
+
+int mdk_plan_open_perread(int argc, char *argv[], mdk_plan **out) { return perread_open(argc, argv, out, 0); }
 
 int mdk_plan_emit_perread(mdk_plan *p, const mdk_chunk *c, const md_pr_count *counts, int64_t n) {
     const batchbuf *b; const char *chrom; int64_t i; char line[10000]; sbuf *ob;
@@ -110,21 +114,57 @@ int mdk_plan_emit_perread_raw(mdk_plan *p, const mdk_chunk *c, const uint32_t *k
     return 0;
 }
 
-int perRead_main(int argc, char *argv[]) {
-    mdk_plan *p = NULL; md_dev *dev = NULL; mdk_chunk ch[2]; int have[2] = {0, 0}; int rc, k = 0, ret = 0, more = 1; devopen_t dop; pthread_t dth; int dth_ok;
-    if(argc > 2) hip_warm_up();
-    rc = mdk_plan_open_perread(argc, argv, &p);
+/* a session's sink for a chunk whose reads the host listed (mdk_plan_emit_perread's rows, MDK_CHUNK_NOREF and MDK_HOST_PREP=1): names and
+ * positions from the plan's list, uploaded to the run's rows on the device */
+static int perread_reads_host(mdk_plan *p, md_dev *dev, const mdk_chunk *c, const md_pr_count *counts, int64_t n) {
+    const batchbuf *b; int32_t *pos; uint64_t *off; int64_t i; sbuf nb = {NULL, 0, 0}; int rc;
+    if(c->index != p->next_emit) { fprintf(stderr, "[mdk] chunks must be emitted in order\n"); return -2; }
+    p->next_emit++;
+    if(c->skipped & ~MDK_CHUNK_NOREF) return 0;
+    b = c->host;
+    if(!b || (int64_t)b->n != c->pr.n_reads || (counts && n != c->pr.n_reads)) return -2;
+    if(!counts && !(c->skipped & MDK_CHUNK_NOREF) && c->pr.n_reads) return -2;
+    if(!c->pr.n_reads) return 0;
+    pos = malloc(sizeof(int32_t) * (size_t)c->pr.n_reads); off = malloc(sizeof(uint64_t) * ((size_t)c->pr.n_reads + 1));
+    if(!pos || !off) { free(pos); free(off); return -5; }
+    for(i = 0; i < c->pr.n_reads; i++) {
+        const char *qn = b->qn + b->ri[i].qn_off;
+        pos[i] = b->ri[i].pos; off[i] = nb.l;
+        sb_put(&nb, qn, strlen(qn));
+    }
+    off[c->pr.n_reads] = nb.l;
+    rc = md_dev_reads_host(dev, c->tid, c->pr.n_reads, pos, counts, off, (const uint8_t *)nb.s);
+    free(pos); free(off); free(nb.s);
+    return rc;
+}
+
+struct mdk_reads { md_reads_set *set; int64_t n, n_bytes; int n_contigs; char **names; };
+
+/* perRead_main's loop; S != NULL: a session's run -- no text, every chunk's rows kept on S's device handle (opened at the first run of the
+ * session, reset before every later one) and handed over in *out */
+static int perread_run(int argc, char *argv[], mdk_session *S, mdk_reads **out) {
+    mdk_plan *p = NULL; md_dev *dev = NULL; mdk_chunk ch[2]; int have[2] = {0, 0}; int rc, k = 0, ret = 0, more = 1, i; devopen_t dop; pthread_t dth; int dth_ok;
+    int slot[2] = {0, 1};
+    if(argc > 2 && !S) hip_warm_up();
+    rc = perread_open(argc, argv, &p, S != NULL);
     if(rc != 0 || !p) return rc;
     memset(&dop, 0, sizeof(dop));
     mdk_plan_dev_cfg(p, &dop.cfg);
-    if(getenv("MDK_DEVICE")) dop.device = atoi(getenv("MDK_DEVICE"));
+    if(S) { session_geometry(&dop.cfg); slot[1] = dop.cfg.n_slots / dop.cfg.n_streams; }       /* (the two chunks in flight on slots of two streams) */
+    else if(getenv("MDK_DEVICE")) dop.device = atoi(getenv("MDK_DEVICE"));
     if(!getenv("MDK_HOST_PREP")) mdk_plan_set_prep(p, 1);       /* the device selects the reads (perRead.c:178-183) and walks them where they lie in the records */
-    dth_ok = pthread_create(&dth, NULL, devopen_main, &dop) == 0;       /* no thread: open the device here, after the pipeline has started */
-    if(!p->started && pipeline_start(p)) { if(dth_ok) pthread_join(dth, NULL); if(dop.dev) md_dev_close(dop.dev); mdk_plan_close(p); return -5; }
-    if(dth_ok) pthread_join(dth, NULL); else devopen_main(&dop);
+    if(S) {
+        if(!p->started && pipeline_start(p)) { mdk_plan_close(p); return -5; }
+        session_device(S, &dop);
+    } else {
+        dth_ok = pthread_create(&dth, NULL, devopen_main, &dop) == 0;       /* no thread: open the device here, after the pipeline has started */
+        if(!p->started && pipeline_start(p)) { if(dth_ok) pthread_join(dth, NULL); if(dop.dev) md_dev_close(dop.dev); mdk_plan_close(p); return -5; }
+        if(dth_ok) pthread_join(dth, NULL); else devopen_main(&dop);
+    }
     dev = dop.dev;
     if(dop.rc) { fprintf(stderr, "[mdk] cannot open MI355X device %d: %s\n[mdk] this build has no CPU path for `perRead`.\n", user_device(dop.device), dop.err); mdk_plan_close(p); return MDK_RC_NODEVICE; }
     if(p->dev_prep) { md_prep_cfg pc; mdk_plan_prep_cfg(p, &pc); md_dev_set_prep(dev, &pc); }
+    if(S && md_dev_reads_begin(dev)) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); mdk_plan_close(p); return MDK_RC_DEVICE; }
     while(more || have[0] || have[1]) {       /* two chunks in flight, as in extract_main */
         int cur = k & 1, prev = cur ^ 1;
         if(more) {
@@ -134,11 +174,12 @@ int perRead_main(int argc, char *argv[]) {
             else {
                 if(ch[cur].prep && !ch[cur].skipped) {
                     rc = mdk_plan_ensure_reference(p, dev, ch[cur].tid);
-                    if(!rc) rc = md_dev_perread_submit_raw(dev, cur, &ch[cur].raw);
+                    if(!rc) rc = md_dev_perread_submit_raw(dev, slot[cur], &ch[cur].raw);
+                    if(!rc && S) rc = md_dev_reads_slot(dev, slot[cur]);
                     if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
                 } else if(!ch[cur].skipped && ch[cur].pr.n_reads) {
                     rc = mdk_plan_ensure_reference(p, dev, ch[cur].tid);
-                    if(!rc) rc = md_dev_perread_submit(dev, cur, &ch[cur].pr);
+                    if(!rc) rc = md_dev_perread_submit(dev, slot[cur], &ch[cur].pr);
                     if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
                 }
                 have[cur] = 1;
@@ -148,27 +189,87 @@ int perRead_main(int argc, char *argv[]) {
             const md_pr_count *cnt = NULL; int64_t n = 0;
             if(ch[prev].prep && !ch[prev].skipped) {
                 const uint32_t *kept = NULL;
-                rc = md_dev_perread_download_raw(dev, prev, &kept, &cnt, &n);
-                if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
-                if(mdk_plan_emit_perread_raw(p, &ch[prev], kept, cnt, n)) { ret = MDK_RC_DEVICE; break; }
+                if(S) {          /* the rows stay on the device */
+                    if(ch[prev].index != p->next_emit) { fprintf(stderr, "[mdk] chunks must be emitted in order\n"); ret = MDK_RC_DEVICE; break; }
+                    p->next_emit++;
+                    rc = md_dev_reads_collect(dev, slot[prev], &n);
+                    if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
+                } else {
+                    rc = md_dev_perread_download_raw(dev, slot[prev], &kept, &cnt, &n);
+                    if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
+                    if(mdk_plan_emit_perread_raw(p, &ch[prev], kept, cnt, n)) { ret = MDK_RC_DEVICE; break; }
+                }
                 have[prev] = 0; k++;
                 if(!more && !have[0] && !have[1]) break;
                 continue;
             }
             if(!ch[prev].skipped && ch[prev].pr.n_reads) {
-                rc = md_dev_perread_download(dev, prev, &cnt, &n);
+                rc = md_dev_perread_download(dev, slot[prev], &cnt, &n);
                 if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
             }
-            if(mdk_plan_emit_perread(p, &ch[prev], cnt, n)) { ret = MDK_RC_DEVICE; break; }
+            if(S) { rc = perread_reads_host(p, dev, &ch[prev], cnt, n); if(rc) { if(rc != -2) fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = rc == -5 ? -5 : MDK_RC_DEVICE; break; } }
+            else if(mdk_plan_emit_perread(p, &ch[prev], cnt, n)) { ret = MDK_RC_DEVICE; break; }
             have[prev] = 0;
         }
         k++;
         if(!more && !have[0] && !have[1]) break;
     }
-    fflush(p->pr_out);
-    if(fast_exit_wanted()) { if(p->pr_out_owned) fclose(p->pr_out); leave_fast_plan(p, ret); }
-    md_dev_close(dev);
+    if(!S) {
+        fflush(p->pr_out);
+        if(fast_exit_wanted()) { if(p->pr_out_owned) fclose(p->pr_out); leave_fast_plan(p, ret); }
+        md_dev_close(dev);
+        mdk_plan_close(p);
+        return ret;
+    }
+    {   /* the rows, in schedule order, handed over with the contig names; the handle's reads state is finished either way */
+        md_reads_set *set = NULL; int frc;
+        (void)md_dev_sync(dev);          /* (after an error a chunk may still be reading the plan's memory) */
+        frc = md_dev_reads_finish(dev, &set);
+        if(!ret && frc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; }
+        if(!ret) {
+            mdk_reads *r = calloc(1, sizeof(*r)); const int nt = p->bam->n_targets;
+            if(r) r->names = calloc((size_t)nt + 1, sizeof(char *));
+            if(!r || !r->names) { free(r); md_reads_set_free(set); ret = -5; }
+            else { r->set = set; r->n = md_reads_set_count(set); r->n_bytes = md_reads_set_name_bytes(set); r->n_contigs = nt; for(i = 0; i < nt; i++) r->names[i] = strdup(p->bam->target_name[i]); *out = r; }
+        } else md_reads_set_free(set);
+    }
     mdk_plan_close(p);
     return ret;
 }
 
+int perRead_main(int argc, char *argv[]) { return perread_run(argc, argv, NULL, NULL); }
+
+/* ---- the session's perRead (include/mdk_extract.h) ---- */
+int mdk_session_perread(mdk_session *s, int argc, char *argv[], mdk_reads **out) {
+    int rc;
+    if(!s || !out || argc < 1 || !argv) return MDK_ERR_ARG;
+    *out = NULL;
+    rc = perread_run(argc, argv, s, out);
+    if(rc == 0 && !*out) { *out = calloc(1, sizeof(mdk_reads)); if(!*out) return -5; }      /* (help / version: no run, no reads) */
+    return rc;
+}
+int64_t mdk_reads_count(const mdk_reads *r) { return r ? r->n : -1; }
+int64_t mdk_reads_name_bytes(const mdk_reads *r) { return r ? r->n_bytes : -1; }
+int mdk_reads_n_contigs(const mdk_reads *r) { return r ? r->n_contigs : -1; }
+const char *mdk_reads_contig_name(const mdk_reads *r, int i) { return (r && i >= 0 && i < r->n_contigs) ? r->names[i] : NULL; }
+int mdk_reads_copy(const mdk_reads *r, int column, void *dst, int to_host) {
+    md_reads_cols d; memset(&d, 0, sizeof(d));
+    if(!r || !dst || column < 0 || column > MDK_READS_NAME_BYTES) return MDK_ERR_ARG;
+    if(!r->set) { if(column == MDK_READS_NAME_OFFSETS) { const int64_t z = 0; if(to_host) memcpy(dst, &z, sizeof(z)); else return MDK_ERR_ARG; } return 0; }     /* (an empty result without a run: one offset, 0) */
+    switch(column) {
+    case MDK_READS_CONTIG: d.contig = dst; break;
+    case MDK_READS_POS: d.pos = dst; break;
+    case MDK_READS_NMETH: d.nmeth = dst; break;
+    case MDK_READS_NUNMETH: d.nunmeth = dst; break;
+    case MDK_READS_NAME_OFFSETS: d.name_off = dst; break;
+    default: d.name_bytes = dst; break;
+    }
+    return md_reads_set_copy(r->set, &d, to_host);
+}
+void mdk_reads_free(mdk_reads *r) {
+    int i;
+    if(!r) return;
+    md_reads_set_free(r->set);
+    for(i = 0; i < r->n_contigs; i++) free(r->names[i]);
+    free(r->names); free(r);
+}

@@ -217,7 +217,6 @@ static void xopen_start(mdk_plan *p, void *arg) {
 }
 
 /* ---- a resident session (include/mdk_extract.h): the same pipeline, one device handle across runs, calls kept on the device ---- */
-struct mdk_session { int device; md_dev *dev; md_dev_cfg cfg; };
 struct mdk_calls { md_calls_set *set; int64_t n; int n_contigs; char **names; };
 /* the session's after_options: options that only shape text or files are refused; the device configuration is worked out as for the command */
 static void session_options(mdk_plan *p, void *arg) {
@@ -227,10 +226,20 @@ static void session_options(mdk_plan *p, void *arg) {
         fprintf(stderr, "[mdk] --fraction, --counts, --logit, --methylKit and --cytosine_report only shape text output: a session returns the calls themselves\n");
         p->open_rc = MDK_RC_UNSUPPORTED; return;
     }
+    mdk_plan_dev_cfg(p, &o->d.cfg);
+    session_geometry(&o->d.cfg);
+}
+MDK_LOCAL void session_geometry(md_dev_cfg *cfg) {
     if(getenv("MDK_GROUPS_IN_FLIGHT")) { g_ngroups = atoi(getenv("MDK_GROUPS_IN_FLIGHT")); if(g_ngroups < 2) g_ngroups = 2; if(g_ngroups > MDK_NGROUPS_MAX) g_ngroups = MDK_NGROUPS_MAX; }
     else g_ngroups = 3;
-    mdk_plan_dev_cfg(p, &o->d.cfg);
-    o->d.cfg.n_slots = MDK_NGROUPS * MDK_GROUP; o->d.cfg.n_streams = MDK_NGROUPS;
+    cfg->n_slots = MDK_NGROUPS * MDK_GROUP; cfg->n_streams = MDK_NGROUPS;
+}
+MDK_LOCAL void session_device(mdk_session *S, devopen_t *d) {
+    d->device = S->device;
+    if(S->dev && (S->cfg.n_slots != d->cfg.n_slots || S->cfg.n_streams != d->cfg.n_streams)) { md_dev_close(S->dev); S->dev = NULL; }
+    if(S->dev) { d->rc = md_dev_reset(S->dev, &d->cfg); d->dev = S->dev; if(d->rc) { snprintf(d->err, sizeof(d->err), "%s", md_dev_last_error()); md_dev_close(S->dev); S->dev = d->dev = NULL; } }
+    else devopen_main(d);
+    S->dev = d->dev; S->cfg = d->cfg;
 }
 
 /* extract_main's pipeline; S != NULL: a session's run -- no output files, no emitter, every collected group compacted into calls on S's device
@@ -251,13 +260,8 @@ static int extract_run(int argc, char *argv[], mdk_session *S, mdk_calls **out) 
     if(!getenv("MDK_HOST_PREP")) mdk_plan_set_prep(p, 1);
     mdk_plan_set_hold(p, MDK_NGROUPS * MDK_GROUP + 2);
     if(!p->started && pipeline_start(p)) { if(dop.started) pthread_join(dop.th, NULL); if(dop.d.dev) md_dev_close(dop.d.dev); mdk_plan_close(p); return -5; }
-    if(S) {          /* the session's handle: opened once, then reset to this run's configuration */
-        dop.d.device = S->device;
-        if(S->dev && (S->cfg.n_slots != dop.d.cfg.n_slots || S->cfg.n_streams != dop.d.cfg.n_streams)) { md_dev_close(S->dev); S->dev = NULL; }
-        if(S->dev) { dop.d.rc = md_dev_reset(S->dev, &dop.d.cfg); dop.d.dev = S->dev; if(dop.d.rc) { snprintf(dop.d.err, sizeof(dop.d.err), "%s", md_dev_last_error()); md_dev_close(S->dev); S->dev = dop.d.dev = NULL; } }
-        else devopen_main(&dop.d);
-        S->dev = dop.d.dev; S->cfg = dop.d.cfg;
-    } else if(dop.started) pthread_join(dop.th, NULL); else { xopen_start(p, &dop); if(dop.started) pthread_join(dop.th, NULL); else devopen_main(&dop.d); }
+    if(S) session_device(S, &dop.d);          /* the session's handle: opened once, then reset to this run's configuration */
+    else if(dop.started) pthread_join(dop.th, NULL); else { xopen_start(p, &dop); if(dop.started) pthread_join(dop.th, NULL); else devopen_main(&dop.d); }
     t_dev = now_s() - T0;
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] resident at device ready %.0f MB\n", rss_mb(0));
     dev = dop.d.dev;

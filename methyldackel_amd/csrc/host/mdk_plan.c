@@ -399,7 +399,7 @@ MDK_LOCAL int plan_open_ex(int argc, char *argv[], mdk_plan **out, void (*after_
     p->shard_rank = 0; p->shard_world = 1;
     p->last_tid = -1; p->last_pos = -1; p->carry_tid = -1;
 
-    optind = 1;     /* the reference relies on a fresh process; being a library we reset getopt */
+    optind = 0;     /* the reference relies on a fresh process; being a library we reset getopt (0: glibc's full reset -- a parse that stopped early, at -h, leaves it pointing into the argv of that call) */
     /* NB -f, -c and -m take an argument in the short-option string although --fraction/--counts/--logit do not
      * (extract.c:796 vs 757-759); kept as is, it is part of the option surface. */
     while((c = getopt_long(argc, argv, "hvq:p:r:l:o:D:f:c:m:d:F:R:@:M:t:b:ON:B:", longopts, NULL)) >= 0) {

@@ -136,6 +136,10 @@ typedef struct {
 
 /* opening the device on its own thread while the host pipeline is already running (mdk_extract.c) */
 typedef struct { int device; md_dev_cfg cfg; md_dev *dev; int rc; char err[512]; } devopen_t;
+/* a resident session (include/mdk_extract.h): one device handle across the runs of every command it serves (mdk_extract.c, mdk_cmd_perread.c) */
+struct mdk_session { int device; md_dev *dev; md_dev_cfg cfg; };
+MDK_LOCAL void session_geometry(md_dev_cfg *cfg);              /* the slots and streams of every session run, whatever its command: switching commands resets the handle */
+MDK_LOCAL void session_device(mdk_session *S, devopen_t *d);   /* the session's handle for a run with d->cfg: opened at the first run, reset before every later one */
 
 MDK_LOCAL void plan_free(mdk_plan *p);
 MDK_LOCAL int plan_open_ex(int argc, char *argv[], mdk_plan **out, void (*after_options)(mdk_plan *, void *), void *ctx);

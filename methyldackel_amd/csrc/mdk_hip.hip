@@ -1090,7 +1090,7 @@ extern "C" void md_dev_close(md_dev *h) {
     if(h->piece_inf) (void)hipStreamDestroy(h->piece_inf);
     if(h->ref_stream) (void)hipStreamDestroy(h->ref_stream);
     g_open_handles.fetch_sub(1);                       // (before the last carved buffers go: the give that brings the count to zero may start the blocks over)
-    calls_state_free(h);
+    calls_state_free(h); reads_state_free(h);
     h->d_status.release(); h->h_status.release();
     if(h->d_crc) (void)hipFree(h->d_crc);
     if(h->d_hist) (void)hipFree(h->d_hist);
@@ -1101,7 +1101,8 @@ extern "C" void md_dev_close(md_dev *h) {
 }
 
 // An idle handle back to what md_dev_open left (a resident service runs one command after another on it): every slot's buffers, the
-// contigs (bases, -l runs, mappability), the preparation settings and the mbias histogram go; streams, events and the loaded code object
+// contigs (bases, -l runs, mappability), the preparation settings (perRead's among them), the mbias histogram and the calls and reads
+// state go, and every slot is as md_dev_open made it (no perRead chunk pending); streams, events and the loaded code object
 // stay.  When this is the only open handle and nothing else is carved, the carved blocks are reused from their start afterwards -- a
 // handle that stayed open would otherwise take fresh carved memory for every run's pieces and slots.
 extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
@@ -1121,6 +1122,7 @@ extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     h->d_hist = nullptr; h->hist_cap = 0; h->hist_len = 0; h->h_hist.clear();
     if(h->calls) { calls_state_free(h); }
     h->no_pack = false;
+    reads_state_free(h); h->reads_on = false;
     for(Slot &s : h->slots) {
         slot_buffers_release(s);
         Slot f;                           // the slot as md_dev_open made it: its stream, events and status block stay

@@ -94,7 +94,7 @@ struct alignas(16) PrepRead {
 // three CIGAR operations travel with the read in cig[] as 21 bits each (length < 2^17 << 4 | operation) under a flag in bit 63 that says they
 // are there; a longer operation, or a fourth one, is read where it lies.
 static_assert(sizeof(PrepRead) == 48, "PrepRead layout");
-struct PrepCounters { uint32_t n_adm, n_segs, malformed, strand0, fallback, max_lq; uint64_t algo_bytes; uint32_t far, pad; };      // max_lq: longest admitted read (mbias sizes its histogram by it)
+struct PrepCounters { uint32_t n_adm, n_segs, malformed, strand0, fallback, max_lq; uint64_t algo_bytes; uint32_t far, name_bytes; };      // max_lq: longest admitted read (mbias sizes its histogram by it); name_bytes: perRead session, the kept reads' names (mdk_reads.hip)
 #define MDK_ERR_PREP_REDO (-100)   // internal: the segment array was enlarged and the preparation re-enqueued
 
 // everything the host reads back after a launch, one block per slot inside ONE device array (and its pinned mirror), so that
@@ -130,9 +130,12 @@ struct Slot {
 
 struct CallsState;                          // mdk_calls.hip
 MDK_HIDDEN void calls_state_free(md_dev *h);
+struct ReadsState;                          // mdk_reads.hip
+MDK_HIDDEN void reads_state_free(md_dev *h);
 struct md_dev {
     int device; md_dev_cfg cfg; int tile, n_slots; bool variant; bool qw = false;
     CallsState *calls = nullptr; bool no_pack = false;     // md_dev_calls_*: the compaction's state; no_pack: group launches leave their sites on the device
+    ReadsState *reads = nullptr; bool reads_on = false;    // md_dev_reads_*: the perRead rows' state; reads_on: md_dev_perread_submit_raw copies nothing back
     std::vector<hipStream_t> streams;        // the streams the slots work on (cfg.n_streams of them, or one per slot)
     std::mutex crc_mu; void *d_crc = nullptr;   // constants of k_crc32 (mdk_inflate.hip), made by the first piece
     std::mutex piece_mu; std::vector<hipStream_t> piece_streams; int piece_rr = 0; hipStream_t piece_in = nullptr, piece_inf = nullptr;      /* the pieces' lanes (mdk_inflate.hip): the stream their compressed bytes cross the link on, the stream k_inflate runs on */      // the pieces' streams: a few, shared (mdk_inflate.hip piece_stream_of)

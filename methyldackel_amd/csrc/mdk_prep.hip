@@ -1289,10 +1289,13 @@ extern "C" int md_dev_perread_submit_raw(md_dev *h, int slot, const md_raw_batch
         int64_t wend = b->end + 10000; if(wend > P.reflen - 1) wend = P.reflen - 1;
         hipLaunchKernelGGL(k_perread_raw, dim3(nb), dim3(PB), 0, s->stream, P, (const uint8_t *)h->refcode[b->tid], wend, s->d_prc.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_aidx.p, s->d_aidx.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipMemcpyAsync(s->h_prc.p, s->d_prc.p, sizeof(md_pr_count) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+        if(!h->reads_on) {
+            HIPCHK(hipMemcpyAsync(s->h_aidx.p, s->d_aidx.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipMemcpyAsync(s->h_prc.p, s->d_prc.p, sizeof(md_pr_count) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
+        }
     }
-    HIPCHK(hipMemcpyAsync(s->h_st.p, h->d_status.p + s->index, sizeof(SlotStatus), hipMemcpyDeviceToHost, s->stream));
+    // a perRead session (md_dev_reads_begin): the kept reads stay on the device, md_dev_reads_slot queues the status copy behind its kernels
+    if(!h->reads_on) HIPCHK(hipMemcpyAsync(s->h_st.p, h->d_status.p + s->index, sizeof(SlotStatus), hipMemcpyDeviceToHost, s->stream));
     s->pr_n = n;
     return 0;
 }

@@ -1,0 +1,328 @@
+// mdk_reads.hip -- the rows of `perRead` as device-resident columns (include/mdk_hip.h, "reads on the device").
+//
+// What addRead (perRead.c:16-36) prints for a kept read -- name, contig, position and the read's CpG calls -- kept as columns for a
+// resident session instead of formatted by the host.  For a chunk the device selected (k_prep_scan_ordered) and walked (k_perread_raw),
+// no per-read data crosses to the host:
+//   k_reads_len     (slot stream, behind k_perread_raw) per kept read the length of its name -- l_read_name, then a bounded scan for
+//                   the first NUL -- and the exclusive scan of those lengths inside its workgroup (ballot-free: wave64 __shfl_up, wave
+//                   totals in LDS); the workgroup's total to a per-slot table;
+//   k_reads_blocks  (slot stream, one workgroup) the exclusive scan of those totals, and the chunk's name bytes into the slot's status
+//                   block, which the host copies back anyway (PrepCounters.name_bytes next to n_adm);
+//   k_reads_rows    (the handle's reads stream, once the host knows the two totals) contig, pos, counts and the int64 name offsets of
+//                   the chunk's rows, at the run arena's exact end;
+//   k_reads_names   (reads stream) the name bytes, one output byte per lane: consecutive lanes store consecutive bytes, each found by
+//                   a binary search over the offsets k_reads_rows wrote.
+// Chunks are appended in the order md_dev_reads_collect is called (the caller's schedule order): the arena needs no final gather.
+#include "mdk_hip_internal.hpp"
+#include <algorithm>
+
+#define READS_WG 256
+#define READS_SCAN_WG 1024
+#define READS_NAME_OFF 36u           // the name's offset from a record's block_size word; l_read_name at +12, pos at +8
+
+struct ReadsSlot { DBuf<uint32_t> loc, boff; };       // per kept read: its name's offset inside its workgroup's; per workgroup: the offset of its names in the chunk
+struct ReadsState {
+    hipStream_t st = nullptr; hipEvent_t done = nullptr;      // the appends run here; `done` orders the slots' next work after them
+    // the run's rows: plain hipMalloc, grown by doubling, kept across runs
+    int32_t *contig = nullptr, *pos = nullptr, *nm = nullptr, *nu = nullptr; int64_t *off = nullptr; uint64_t cap_rows = 0, used_rows = 0;
+    uint8_t *bytes = nullptr; uint64_t cap_bytes = 0, used_bytes = 0;
+    std::vector<ReadsSlot> slots;
+};
+
+struct md_reads_set {
+    int device = 0; int64_t n = 0, n_bytes = 0;
+    int32_t *contig = nullptr, *pos = nullptr, *nm = nullptr, *nu = nullptr; int64_t *off = nullptr; uint8_t *bytes = nullptr;
+    void *mem = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------
+// kernels
+// ------------------------------------------------------------------------------------------------
+// exclusive scan of v over the workgroup (WGS threads, waves of 64): wave scan with __shfl_up, wave totals through LDS
+template <int WGS>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wtot, uint32_t &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = v;
+    for(int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if(lane >= d) x += y; }
+    if(lane == 63) wtot[wave] = x;
+    __syncthreads();
+    uint32_t before = 0; total = 0;
+    for(int w = 0; w < WGS / 64; w++) { const uint32_t t = wtot[w]; if(w < wave) before += t; total += t; }
+    __syncthreads();                 // (wtot may be rewritten by the caller's next round)
+    return before + x - v;
+}
+
+struct KReadsScan { const uint8_t *raw; uint64_t raw_span; const uint32_t *rec_at, *aidx; PrepCounters *cnt; uint32_t *loc, *boff; };
+
+// the name of the record at `o`: l_read_name bytes up to the first NUL, never past the chunk's records
+__device__ __forceinline__ uint32_t name_len(const uint8_t *raw, uint64_t raw_span, uint32_t o) {
+    if((uint64_t)o + READS_NAME_OFF > raw_span) return 0;
+    const uint64_t room = raw_span - o - READS_NAME_OFF;
+    const uint32_t lim = room < raw[o + 12] ? (uint32_t)room : (uint32_t)raw[o + 12];
+    const uint8_t *q = raw + o + READS_NAME_OFF;
+    uint32_t k = 0;
+    for(; k + 4 <= lim; k += 4) {                  // a word at a time while it stays inside l_read_name
+        uint32_t w; __builtin_memcpy(&w, q + k, 4);
+        if(!(w & 0xffu)) return k;
+        if(!(w & 0xff00u)) return k + 1;
+        if(!(w & 0xff0000u)) return k + 2;
+        if(!(w & 0xff000000u)) return k + 3;
+    }
+    for(; k < lim; k++) if(!q[k]) return k;
+    return lim;
+}
+
+__global__ __launch_bounds__(READS_WG) void k_reads_len(const KReadsScan K) {
+    __shared__ uint32_t wtot[READS_WG / 64];
+    const uint32_t n = K.cnt->n_adm;
+    if(blockIdx.x * READS_WG >= n) return;                      // (the grid covers every candidate record; the kept ones are fewer)
+    const uint32_t a = blockIdx.x * READS_WG + threadIdx.x;
+    const uint32_t len = a < n ? name_len(K.raw, K.raw_span, K.rec_at[K.aidx[a]]) : 0u;
+    uint32_t total;
+    const uint32_t ex = block_excl_scan<READS_WG>(len, wtot, total);
+    if(a < n) K.loc[a] = ex;
+    if(threadIdx.x == 0) K.boff[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(READS_SCAN_WG) void k_reads_blocks(const KReadsScan K) {
+    __shared__ uint32_t wtot[READS_SCAN_WG / 64];
+    const uint32_t n = K.cnt->n_adm, nb = (n + READS_WG - 1) / READS_WG;
+    uint32_t carry = 0;
+    for(uint32_t b0 = 0; b0 < nb; b0 += READS_SCAN_WG) {        // (uniform trip count: every thread takes part in every scan)
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < nb ? K.boff[b] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan<READS_SCAN_WG>(v, wtot, total);
+        if(b < nb) K.boff[b] = carry + ex;
+        carry += total;
+    }
+    if(threadIdx.x == 0) K.cnt->name_bytes = carry;
+}
+
+struct KReadsRows {
+    const uint8_t *raw; const uint32_t *rec_at, *aidx, *loc, *boff; const md_pr_count *prc; uint32_t n, total; int32_t tid;
+    uint64_t row, byte_base;
+    int32_t *contig, *pos, *nm, *nu; int64_t *off;
+};
+__global__ __launch_bounds__(READS_WG) void k_reads_rows(const KReadsRows K) {
+    const uint32_t a = blockIdx.x * READS_WG + threadIdx.x;
+    if(a > K.n) return;
+    const uint64_t r = K.row + a;
+    if(a == K.n) { K.off[r] = (int64_t)(K.byte_base + K.total); return; }      // the end of the chunk's names (the next chunk's first offset)
+    int32_t p; __builtin_memcpy(&p, K.raw + K.rec_at[K.aidx[a]] + 8, 4);
+    const md_pr_count c = K.prc[a];
+    K.contig[r] = K.tid; K.pos[r] = p; K.nm[r] = (int32_t)c.nmeth; K.nu[r] = (int32_t)c.nunmeth;
+    K.off[r] = (int64_t)(K.byte_base + K.boff[a / READS_WG] + K.loc[a]);
+}
+
+struct KReadsNames { const uint8_t *raw; const uint32_t *rec_at, *aidx; const int64_t *off; uint32_t n, total; uint64_t row, byte_base; uint8_t *bytes; };
+// the largest a in [lo, hi] with off[a] <= p (off ascending, off[lo] <= p)
+__device__ __forceinline__ uint32_t reads_find(const int64_t *off, uint32_t lo, uint32_t hi, int64_t p) {
+    while(lo < hi) { const uint32_t m = lo + (hi - lo + 1) / 2; if(off[m] <= p) lo = m; else hi = m - 1; }
+    return lo;
+}
+__global__ __launch_bounds__(READS_WG) void k_reads_names(const KReadsNames K) {
+    __shared__ uint32_t s_lo, s_hi;
+    const int64_t *off = K.off + K.row;                          // off[0 .. n]: this chunk's rows, absolute
+    for(uint64_t t0 = (uint64_t)blockIdx.x * READS_WG; t0 < K.total; t0 += (uint64_t)gridDim.x * READS_WG) {
+        const uint64_t last = (t0 + READS_WG < K.total ? t0 + READS_WG : (uint64_t)K.total) - 1;
+        if(threadIdx.x == 0) s_lo = reads_find(off, 0, K.n - 1, (int64_t)(K.byte_base + t0));
+        if(threadIdx.x == 1) s_hi = reads_find(off, 0, K.n - 1, (int64_t)(K.byte_base + last));
+        __syncthreads();
+        const uint64_t j = t0 + threadIdx.x;
+        if(j < K.total) {
+            const int64_t p = (int64_t)(K.byte_base + j);
+            const uint32_t a = reads_find(off, s_lo, s_hi, p);
+            K.bytes[p] = K.raw[K.rec_at[K.aidx[a]] + READS_NAME_OFF + (uint64_t)(p - off[a])];
+        }
+        __syncthreads();             // (s_lo / s_hi are rewritten by the next tile)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+static void reads_free_arena(ReadsState *r) {
+    for(void *p : {(void *)r->contig, (void *)r->pos, (void *)r->nm, (void *)r->nu, (void *)r->off}) if(p) (void)hipFree(p);
+    r->contig = r->pos = r->nm = r->nu = nullptr; r->off = nullptr; r->cap_rows = 0;
+    if(r->bytes) (void)hipFree(r->bytes);
+    r->bytes = nullptr; r->cap_bytes = 0;
+}
+// room for `rows` more rows (and the end offset behind them) and `bytes` more name bytes.  Growing copies what is there: every append
+// queued so far is waited for first.
+static int reads_reserve(ReadsState *r, uint64_t rows, uint64_t bytes) {
+    if(r->used_rows + rows + 1 > r->cap_rows) {
+        const uint64_t want = std::max<uint64_t>(r->cap_rows * 2, std::max<uint64_t>(r->used_rows + rows + 1, 1u << 18));
+        HIPCHK(hipStreamSynchronize(r->st));
+        int32_t *c = nullptr, *p = nullptr, *m = nullptr, *u = nullptr; int64_t *o = nullptr;
+        hipError_t e = hipMalloc((void **)&c, want * 4);
+        if(e == hipSuccess) e = hipMalloc((void **)&p, want * 4);
+        if(e == hipSuccess) e = hipMalloc((void **)&m, want * 4);
+        if(e == hipSuccess) e = hipMalloc((void **)&u, want * 4);
+        if(e == hipSuccess) e = hipMalloc((void **)&o, want * 8);
+        if(e != hipSuccess) { for(void *q : {(void *)c, (void *)p, (void *)m, (void *)u, (void *)o}) if(q) (void)hipFree(q); return fail(MDK_ERR_NOMEM, "hipMalloc(read rows)", e); }
+        if(r->used_rows) {
+            const size_t n = (size_t)r->used_rows;
+            HIPCHK(hipMemcpyAsync(c, r->contig, n * 4, hipMemcpyDeviceToDevice, r->st)); HIPCHK(hipMemcpyAsync(p, r->pos, n * 4, hipMemcpyDeviceToDevice, r->st));
+            HIPCHK(hipMemcpyAsync(m, r->nm, n * 4, hipMemcpyDeviceToDevice, r->st)); HIPCHK(hipMemcpyAsync(u, r->nu, n * 4, hipMemcpyDeviceToDevice, r->st));
+            HIPCHK(hipMemcpyAsync(o, r->off, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
+            HIPCHK(hipStreamSynchronize(r->st));
+        }
+        for(void *q : {(void *)r->contig, (void *)r->pos, (void *)r->nm, (void *)r->nu, (void *)r->off}) if(q) (void)hipFree(q);
+        r->contig = c; r->pos = p; r->nm = m; r->nu = u; r->off = o; r->cap_rows = want;
+    }
+    if(r->used_bytes + bytes > r->cap_bytes) {
+        const uint64_t want = std::max<uint64_t>(r->cap_bytes * 2, std::max<uint64_t>(r->used_bytes + bytes, 1u << 22));
+        HIPCHK(hipStreamSynchronize(r->st));
+        uint8_t *b = nullptr;
+        hipError_t e = hipMalloc((void **)&b, want);
+        if(e != hipSuccess) return fail(MDK_ERR_NOMEM, "hipMalloc(read names)", e);
+        if(r->used_bytes) { e = hipMemcpy(b, r->bytes, (size_t)r->used_bytes, hipMemcpyDeviceToDevice); if(e != hipSuccess) { (void)hipFree(b); return fail(MDK_ERR_HIP, "hipMemcpy(read names)", e); } }
+        if(r->bytes) (void)hipFree(r->bytes);
+        r->bytes = b; r->cap_bytes = want;
+    }
+    return 0;
+}
+
+void reads_state_free(md_dev *h) {
+    ReadsState *r = h->reads; if(!r) return;
+    if(r->st) (void)hipStreamSynchronize(r->st);
+    reads_free_arena(r);
+    for(ReadsSlot &s : r->slots) { s.loc.release(); s.boff.release(); }
+    if(r->done) (void)hipEventDestroy(r->done);
+    if(r->st) (void)hipStreamDestroy(r->st);
+    delete r; h->reads = nullptr; h->reads_on = false;
+}
+
+extern "C" int md_dev_reads_begin(md_dev *h) {
+    if(!h) return fail(MDK_ERR_ARG, "md_dev_reads_begin", hipSuccess);
+    HIPCHK(hipSetDevice(h->device));
+    if(!h->reads) h->reads = new ReadsState();
+    ReadsState *r = h->reads;
+    if(!r->st) { r->st = mdk_stream_take(h->device); if(!r->st) return fail(MDK_ERR_HIP, "hipStreamCreateWithFlags", hipGetLastError()); }
+    if(!r->done) HIPCHK(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
+    HIPCHK(hipStreamSynchronize(r->st));
+    if(r->slots.size() < (size_t)h->n_slots) r->slots.resize((size_t)h->n_slots);
+    r->used_rows = 0; r->used_bytes = 0;
+    h->reads_on = true;
+    return 0;
+}
+
+extern "C" int md_dev_reads_slot(md_dev *h, int slot) {
+    Slot *s = get_slot(h, slot);
+    if(!s || !h->reads || !h->reads_on || s->pr_n < 0 || !s->raw_layout) return fail(MDK_ERR_ARG, "md_dev_reads_slot: md_dev_reads_begin and md_dev_perread_submit_raw on the slot first", hipSuccess);
+    HIPCHK(hipSetDevice(h->device));
+    ReadsSlot &rs = h->reads->slots[(size_t)slot];
+    const int n = s->pr_nrec, nb = (n + READS_WG - 1) / READS_WG;
+    if(rs.loc.need((size_t)n + 1) || rs.boff.need((size_t)nb + 1)) return MDK_ERR_NOMEM;
+    KReadsScan K; K.raw = s->raw_at; K.raw_span = s->raw_span; K.rec_at = s->rec_at; K.aidx = s->d_aidx.p; K.cnt = s->d_pcnt.p; K.loc = rs.loc.p; K.boff = rs.boff.p;
+    if(nb > 0) hipLaunchKernelGGL(k_reads_len, dim3((unsigned)nb), dim3(READS_WG), 0, s->stream, K);
+    hipLaunchKernelGGL(k_reads_blocks, dim3(1), dim3(READS_SCAN_WG), 0, s->stream, K);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->h_st.p, h->d_status.p + s->index, sizeof(SlotStatus), hipMemcpyDeviceToHost, s->stream));
+    return 0;
+}
+
+extern "C" int md_dev_reads_collect(md_dev *h, int slot, int64_t *n_out) {
+    Slot *s = get_slot(h, slot);
+    if(!s || !n_out || !h->reads || !h->reads_on || s->pr_n < 0) return fail(MDK_ERR_ARG, "md_dev_reads_collect: nothing submitted on this slot", hipSuccess);
+    *n_out = 0;
+    HIPCHK(hipSetDevice(h->device));
+    ReadsState *r = h->reads; ReadsSlot &rs = r->slots[(size_t)slot];
+    HIPCHK(hipStreamSynchronize(s->stream));
+    const PrepCounters &c = s->h_st.p->pc;
+    if(c.malformed) { snprintf(mdk_err_buf(), MDK_ERR_BYTES, "malformed BAM record in the chunk"); return MDK_ERR_ARG; }
+    const uint32_t n = c.n_adm, total = c.name_bytes;
+    if(n > (uint32_t)std::max(s->pr_nrec, 0) || total > s->raw_span) return fail(MDK_ERR_ARG, "md_dev_reads_collect: inconsistent counts", hipSuccess);
+    if(n == 0) return 0;
+    { const int rc = reads_reserve(r, n, total); if(rc) return rc; }
+    KReadsRows R; R.raw = s->raw_at; R.rec_at = s->rec_at; R.aidx = s->d_aidx.p; R.loc = rs.loc.p; R.boff = rs.boff.p; R.prc = s->d_prc.p; R.n = n; R.total = total; R.tid = s->tid;
+    R.row = r->used_rows; R.byte_base = r->used_bytes; R.contig = r->contig; R.pos = r->pos; R.nm = r->nm; R.nu = r->nu; R.off = r->off;
+    hipLaunchKernelGGL(k_reads_rows, dim3((n + 1 + READS_WG - 1) / READS_WG), dim3(READS_WG), 0, r->st, R);
+    if(total) {
+        KReadsNames N; N.raw = s->raw_at; N.rec_at = s->rec_at; N.aidx = s->d_aidx.p; N.off = r->off; N.n = n; N.total = total; N.row = r->used_rows; N.byte_base = r->used_bytes; N.bytes = r->bytes;
+        const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)total + READS_WG - 1) / READS_WG, 1u << 16);
+        hipLaunchKernelGGL(k_reads_names, dim3(grid), dim3(READS_WG), 0, r->st, N);
+    }
+    HIPCHK(hipGetLastError());
+    // the slot's next submit comes after the appends have read its records, kept reads and counts
+    HIPCHK(hipEventRecord(r->done, r->st));
+    HIPCHK(hipStreamWaitEvent(s->stream, r->done, 0));
+    r->used_rows += n; r->used_bytes += total;
+    *n_out = n;
+    return 0;
+}
+
+extern "C" int md_dev_reads_host(md_dev *h, int32_t tid, int64_t n, const int32_t *pos, const md_pr_count *counts, const uint64_t *name_off, const uint8_t *names) {
+    if(!h || !h->reads || !h->reads_on || tid < 0 || n < 0 || (n && (!pos || !name_off || (name_off[n] > name_off[0] && !names)))) return fail(MDK_ERR_ARG, "md_dev_reads_host", hipSuccess);
+    if(n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    ReadsState *r = h->reads;
+    const uint64_t total = name_off[n] - name_off[0];
+    { const int rc = reads_reserve(r, (uint64_t)n, total); if(rc) return rc; }
+    std::vector<int32_t> ct((size_t)n, tid), nm((size_t)n, 0), nu((size_t)n, 0); std::vector<int64_t> off((size_t)n + 1);
+    for(int64_t i = 0; i < n; i++) { if(counts) { nm[(size_t)i] = (int32_t)counts[i].nmeth; nu[(size_t)i] = (int32_t)counts[i].nunmeth; } off[(size_t)i] = (int64_t)(r->used_bytes + name_off[i] - name_off[0]); }
+    off[(size_t)n] = (int64_t)(r->used_bytes + total);
+    const size_t row = (size_t)r->used_rows;
+    HIPCHK(hipMemcpyAsync(r->contig + row, ct.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
+    HIPCHK(hipMemcpyAsync(r->pos + row, pos, (size_t)n * 4, hipMemcpyHostToDevice, r->st));
+    HIPCHK(hipMemcpyAsync(r->nm + row, nm.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
+    HIPCHK(hipMemcpyAsync(r->nu + row, nu.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
+    HIPCHK(hipMemcpyAsync(r->off + row, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, r->st));
+    if(total) HIPCHK(hipMemcpyAsync(r->bytes + r->used_bytes, names + name_off[0], (size_t)total, hipMemcpyHostToDevice, r->st));
+    HIPCHK(hipStreamSynchronize(r->st));        // (the host arrays go when this returns)
+    r->used_rows += (uint64_t)n; r->used_bytes += total;
+    return 0;
+}
+
+extern "C" int md_dev_reads_finish(md_dev *h, md_reads_set **out) {
+    if(!h || !out || !h->reads || !h->reads_on) return fail(MDK_ERR_ARG, "md_dev_reads_finish", hipSuccess);
+    *out = nullptr;
+    HIPCHK(hipSetDevice(h->device));
+    ReadsState *r = h->reads;
+    h->reads_on = false;
+    HIPCHK(hipStreamSynchronize(r->st));
+    md_reads_set *q = new md_reads_set(); q->device = h->device; q->n = (int64_t)r->used_rows; q->n_bytes = (int64_t)r->used_bytes;
+    const size_t n = (size_t)q->n, a4 = (n * 4 + 255) & ~(size_t)255, a8 = ((n + 1) * 8 + 255) & ~(size_t)255, ab = ((size_t)q->n_bytes + 255) & ~(size_t)255;
+    hipError_t e = hipMalloc(&q->mem, 4 * a4 + a8 + ab + 256);
+    if(e != hipSuccess) { delete q; return fail(MDK_ERR_NOMEM, "hipMalloc(reads)", e); }
+    char *m = (char *)q->mem;
+    q->contig = (int32_t *)m; q->pos = (int32_t *)(m + a4); q->nm = (int32_t *)(m + 2 * a4); q->nu = (int32_t *)(m + 3 * a4); q->off = (int64_t *)(m + 4 * a4); q->bytes = (uint8_t *)(m + 4 * a4 + a8);
+    if(n) {
+        e = hipMemcpyAsync(q->contig, r->contig, n * 4, hipMemcpyDeviceToDevice, r->st);
+        if(e == hipSuccess) e = hipMemcpyAsync(q->pos, r->pos, n * 4, hipMemcpyDeviceToDevice, r->st);
+        if(e == hipSuccess) e = hipMemcpyAsync(q->nm, r->nm, n * 4, hipMemcpyDeviceToDevice, r->st);
+        if(e == hipSuccess) e = hipMemcpyAsync(q->nu, r->nu, n * 4, hipMemcpyDeviceToDevice, r->st);
+        if(e == hipSuccess) e = hipMemcpyAsync(q->off, r->off, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st);
+        if(e == hipSuccess && q->n_bytes) e = hipMemcpyAsync(q->bytes, r->bytes, (size_t)q->n_bytes, hipMemcpyDeviceToDevice, r->st);
+    } else e = hipMemsetAsync(q->off, 0, 8, r->st);
+    if(e == hipSuccess) e = hipStreamSynchronize(r->st);
+    if(e != hipSuccess) { (void)hipFree(q->mem); delete q; return fail(MDK_ERR_HIP, "md_dev_reads_finish: copies", e); }
+    r->used_rows = 0; r->used_bytes = 0;
+    *out = q;
+    return 0;
+}
+
+extern "C" int64_t md_reads_set_count(const md_reads_set *r) { return r ? r->n : MDK_ERR_ARG; }
+extern "C" int64_t md_reads_set_name_bytes(const md_reads_set *r) { return r ? r->n_bytes : MDK_ERR_ARG; }
+
+extern "C" int md_reads_set_copy(const md_reads_set *r, const md_reads_cols *dst, int to_host) {
+    if(!r || !dst) return fail(MDK_ERR_ARG, "md_reads_set_copy", hipSuccess);
+    HIPCHK(hipSetDevice(r->device));
+    const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t n = (size_t)r->n;
+    if(dst->name_off) HIPCHK(hipMemcpy(dst->name_off, r->off, (n + 1) * 8, kind));
+    if(dst->name_bytes && r->n_bytes) HIPCHK(hipMemcpy(dst->name_bytes, r->bytes, (size_t)r->n_bytes, kind));
+    if(!n) return 0;
+    if(dst->contig) HIPCHK(hipMemcpy(dst->contig, r->contig, n * 4, kind));
+    if(dst->pos) HIPCHK(hipMemcpy(dst->pos, r->pos, n * 4, kind));
+    if(dst->nmeth) HIPCHK(hipMemcpy(dst->nmeth, r->nm, n * 4, kind));
+    if(dst->nunmeth) HIPCHK(hipMemcpy(dst->nunmeth, r->nu, n * 4, kind));
+    return 0;
+}
+
+extern "C" void md_reads_set_free(md_reads_set *r) {
+    if(!r) return;
+    if(r->mem) { (void)hipSetDevice(r->device); (void)hipFree(r->mem); }
+    delete r;
+}

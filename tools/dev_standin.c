@@ -7,6 +7,8 @@
  * counting itself is what the GPU tests check, everything AROUND it is what runs here.  MDK_STANDIN_HANDBACK=k makes every k-th uploaded chunk
  * come back with MDK_ERR_PREP_HOST once, as a chunk with an over-long read-name chain does on the device; MDK_STANDIN_US_PER_KREC=t makes a
  * chunk take t microseconds per 1000 records on the "device" ("compute time" in the background, for the work balance between ranks).
+ * perRead (tests/test_reads_cpu.py): a chunk's reads are selected from its records as the device selects them, and their counts are the
+ * oracle's `perRead` lines for the same command line, in order (MDK_STANDIN_PERREAD); md_dev_reads_* keep the rows in host memory.
  *   build: gcc -O2 -shared -fPIC -Iinclude -o tools/_build/libmdk_dev_standin.so tools/dev_standin.c -lz -lpthread */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -31,8 +33,11 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 typedef struct { double ready_at; int used, launched, handed_back; int32_t tid; int64_t beg, end; uint8_t *raw; uint64_t raw_bytes, raw_cap; uint32_t *off; uint32_t n_rec, off_cap; md_site *site; md_site_var *var; int64_t cap; } sslot;
 typedef struct { int32_t start, end, nm, nu; uint8_t ctx; int8_t strand; } crow_t;
 typedef struct { uint32_t key; int32_t tid; crow_t *row; int64_t n; } cchunk_t;
+typedef struct { uint32_t *kept; md_pr_count *cnt; int64_t n, cap; int pending; } prslot_t;       /* perRead: the kept reads of a slot's chunk and their counts */
 struct md_dev { md_dev_cfg cfg; int n_slots; sslot *slot; long n_up; int handback; pthread_mutex_t mu; double busy_until; int us_per_krec;
-                md_calls_cfg ccfg; int calls_on; cchunk_t *cch; int n_cch, cap_cch; };
+                md_calls_cfg ccfg; int calls_on; cchunk_t *cch; int n_cch, cap_cch;
+                md_prep_cfg prep; prslot_t *pr; int64_t pr_next;           /* pr_next: the oracle's perRead line the next kept read must match */
+                int reads_on; int32_t *r_contig, *r_pos, *r_nm, *r_nu; int64_t *r_off; uint8_t *r_bytes; int64_t r_n, r_cap, r_nb, r_capb; };
 const char *md_dev_last_error(void) { return t_err; }
 int md_dev_count(void) { return 1; }
 int md_dev_warm(int device) { (void)device; return 0; }
@@ -49,13 +54,18 @@ int md_dev_open(int device, const md_dev_cfg *cfg, md_dev **out) {
     *out = h; return h->slot ? 0 : MDK_ERR_NOMEM;
 }
 static void calls_drop(md_dev *h) { int i; for(i = 0; i < h->n_cch; i++) free(h->cch[i].row); free(h->cch); h->cch = NULL; h->n_cch = h->cap_cch = 0; h->calls_on = 0; }
-void md_dev_close(md_dev *h) { int i; if(!h) return; calls_drop(h); for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); } free(h->slot); free(h); }
+static void reads_drop(md_dev *h) { free(h->r_contig); free(h->r_pos); free(h->r_nm); free(h->r_nu); free(h->r_off); free(h->r_bytes); h->r_contig = h->r_pos = h->r_nm = h->r_nu = NULL; h->r_off = NULL; h->r_bytes = NULL; h->r_n = h->r_cap = h->r_nb = h->r_capb = 0; h->reads_on = 0; }
+void md_dev_close(md_dev *h) {
+    int i; if(!h) return; calls_drop(h); reads_drop(h);
+    for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); if(h->pr) { free(h->pr[i].kept); free(h->pr[i].cnt); } }
+    free(h->pr); free(h->slot); free(h);
+}
 int md_dev_tile(const md_dev *h) { (void)h; return 2048; }
 int md_dev_reserve_contigs(md_dev *h, int32_t n) { (void)h; (void)n; return 0; }
 int md_dev_set_reference(md_dev *h, int32_t tid, const char *seq, int64_t len) { (void)h; (void)tid; (void)seq; (void)len; return 0; }
 int md_dev_set_regions(md_dev *h, int32_t tid, const md_region *runs, int64_t n) { (void)h; (void)tid; (void)runs; (void)n; return 0; }
 int md_dev_set_mappability(md_dev *h, int32_t tid, const uint32_t *bits, int64_t n) { (void)h; (void)tid; (void)bits; (void)n; return 0; }
-int md_dev_set_prep(md_dev *h, const md_prep_cfg *cfg) { (void)h; (void)cfg; return 0; }
+int md_dev_set_prep(md_dev *h, const md_prep_cfg *cfg) { if(h && cfg) h->prep = *cfg; return 0; }
 int md_dev_pci_bus_id(const md_dev *h, char *buf, int cap) { (void)h; snprintf(buf, (size_t)cap, "standin:00.0"); return 0; }      /* every rank "on the same device": the site buffers travel over the ranks' TCP connections */
 int md_dev_profile_text(char *buf, int cap) { if(buf && cap > 0) snprintf(buf, (size_t)cap, "device stand-in (tools/dev_standin.c)"); return 0; }
 void *md_host_alloc(uint64_t bytes) { return malloc((size_t)bytes + 64); }
@@ -140,8 +150,8 @@ struct md_calls_set { int64_t n; int32_t *contig, *start, *end, *nm, *nu; uint8_
 int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     int i;
     if(!h || !cfg || (cfg->n_slots > 0 ? cfg->n_slots : 2) != h->n_slots) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reset"); return MDK_ERR_ARG; }
-    calls_drop(h);
-    for(i = 0; i < h->n_slots; i++) { sslot *s = &h->slot[i]; s->used = s->launched = s->handed_back = 0; s->ready_at = 0; }
+    calls_drop(h); reads_drop(h); memset(&h->prep, 0, sizeof(h->prep));
+    for(i = 0; i < h->n_slots; i++) { sslot *s = &h->slot[i]; s->used = s->launched = s->handed_back = 0; s->ready_at = 0; if(h->pr) h->pr[i].pending = 0; }
     h->cfg = *cfg;
     return 0;
 }
@@ -231,3 +241,114 @@ int md_calls_set_copy(const md_calls_set *c, const md_calls_cols *d, int to_host
     return 0;
 }
 void md_calls_set_free(md_calls_set *c) { if(!c) return; free(c->contig); free(c->start); free(c->end); free(c->nm); free(c->nu); free(c->ctx); free(c->strand); free(c); }
+
+/* ---- perRead: the device's selection of a chunk's reads (perRead.c:178-183, k_prep_scan_ordered) restated over the uploaded records; the
+ * counts (k_perread_raw's) are taken in order from the oracle's `perRead` output for the same command line (MDK_STANDIN_PERREAD), and each
+ * kept read's name and position must be the line's ---- */
+typedef struct { char *name; int32_t pos; uint32_t nm, nu; } prline_t;
+static prline_t *g_pr; static int64_t g_npr; static pthread_once_t g_pr_once = PTHREAD_ONCE_INIT;
+static void load_perread(void) {
+    const char *fn = getenv("MDK_STANDIN_PERREAD"); FILE *f = fn ? fopen(fn, "r") : NULL; char line[4096]; int64_t cap = 0;
+    if(!f) return;
+    while(fgets(line, sizeof line, f)) {
+        char *t[5]; int k = 0; char *q = line;
+        for(k = 0; k < 5; k++) { t[k] = strsep(&q, "\t\n"); if(!t[k]) break; }
+        if(k < 5) continue;
+        if(g_npr == cap) { cap = cap ? 2 * cap : 1 << 14; g_pr = realloc(g_pr, sizeof(prline_t) * (size_t)cap); if(!g_pr) abort(); }
+        { const uint32_t tot = (uint32_t)strtoul(t[4], NULL, 10); const double pct = strtod(t[3], NULL); const uint32_t m = (uint32_t)(pct * tot / 100.0 + 0.5);
+          g_pr[g_npr].name = strdup(t[0]); g_pr[g_npr].pos = (int32_t)strtol(t[2], NULL, 10); g_pr[g_npr].nm = m; g_pr[g_npr].nu = tot - m; g_npr++; }
+    }
+    fclose(f);
+}
+int md_dev_perread_submit_raw(md_dev *h, int slot, const md_raw_batch *b) {
+    sslot *s = slot_of(h, slot); prslot_t *q; uint32_t i; int rc;
+    pthread_once(&g_pr_once, load_perread);
+    if(!s || !b) return MDK_ERR_ARG;
+    if(!h->prep.perread) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_set_prep with perread first"); return MDK_ERR_ARG; }
+    if(!h->pr && !(h->pr = calloc((size_t)h->n_slots, sizeof(prslot_t)))) return MDK_ERR_NOMEM;
+    if((rc = md_dev_upload_raw(h, slot, b)) != 0) return rc;
+    q = &h->pr[slot]; q->n = 0; q->pending = 1;
+    if(q->cap < (int64_t)s->n_rec + 1) { free(q->kept); free(q->cnt); q->cap = (int64_t)s->n_rec + 1024; q->kept = malloc(sizeof(uint32_t) * (size_t)q->cap); q->cnt = malloc(sizeof(md_pr_count) * (size_t)q->cap); if(!q->kept || !q->cnt) return MDK_ERR_NOMEM; }
+    for(i = 0; i < s->n_rec; i++) {
+        const uint8_t *r = s->raw + s->off[i] + 4; int32_t pos; uint16_t flag; const uint8_t mapq = r[9], lqn = r[8]; const prline_t *L; size_t nl;
+        memcpy(&pos, r + 4, 4); memcpy(&flag, r + 14, 2);
+        if((int64_t)pos < b->beg || (int64_t)pos >= b->end) continue;
+        if(h->prep.require_flags && (h->prep.require_flags & flag) != h->prep.require_flags) continue;
+        if(h->prep.ignore_flags && (h->prep.ignore_flags & flag) != 0) continue;
+        if((int)mapq < h->prep.min_mapq) continue;
+        if(h->pr_next >= g_npr) { snprintf(t_err, sizeof t_err, "dev_standin: kept read %lld is past the oracle's perRead lines", (long long)h->pr_next); return MDK_ERR_ARG; }
+        L = &g_pr[h->pr_next++]; nl = strnlen((const char *)r + 32, lqn);
+        if((int32_t)L->pos != pos || strlen(L->name) != nl || memcmp(L->name, r + 32, nl)) { snprintf(t_err, sizeof t_err, "dev_standin: kept read %.60s at %d, the oracle's line is %.60s at %d", (const char *)r + 32, pos, L->name, L->pos); return MDK_ERR_ARG; }
+        q->kept[q->n] = i; q->cnt[q->n].nmeth = L->nm; q->cnt[q->n].nunmeth = L->nu; q->n++;
+    }
+    return 0;
+}
+int md_dev_perread_download_raw(md_dev *h, int slot, const uint32_t **kept, const md_pr_count **counts, int64_t *n) {
+    if(!slot_of(h, slot) || !h->pr || !h->pr[slot].pending || !kept || !counts || !n) { snprintf(t_err, sizeof t_err, "dev_standin: nothing submitted on this slot"); return MDK_ERR_ARG; }
+    *kept = h->pr[slot].kept; *counts = h->pr[slot].cnt; *n = h->pr[slot].n;
+    return 0;
+}
+
+/* ---- reads on the "device": the rows of csrc/mdk_reads.hip, in host memory ---- */
+struct md_reads_set { int64_t n, nb; int32_t *contig, *pos, *nm, *nu; int64_t *off; uint8_t *bytes; };
+int md_dev_reads_begin(md_dev *h) { if(!h) return MDK_ERR_ARG; reads_drop(h); h->reads_on = 1; h->pr_next = 0; return 0; }
+int md_dev_reads_slot(md_dev *h, int slot) { if(!slot_of(h, slot) || !h->reads_on || !h->pr || !h->pr[slot].pending) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reads_slot"); return MDK_ERR_ARG; } return 0; }
+static int reads_room(md_dev *h, int64_t n, int64_t nb) {
+    if(h->r_n + n + 1 > h->r_cap) {
+        const int64_t c = 2 * (h->r_n + n + 1) + 1024;
+        h->r_contig = realloc(h->r_contig, 4 * (size_t)c); h->r_pos = realloc(h->r_pos, 4 * (size_t)c); h->r_nm = realloc(h->r_nm, 4 * (size_t)c); h->r_nu = realloc(h->r_nu, 4 * (size_t)c); h->r_off = realloc(h->r_off, 8 * (size_t)c);
+        if(!h->r_contig || !h->r_pos || !h->r_nm || !h->r_nu || !h->r_off) return MDK_ERR_NOMEM;
+        h->r_cap = c;
+    }
+    if(h->r_nb + nb > h->r_capb) { const int64_t c = 2 * (h->r_nb + nb) + 4096; h->r_bytes = realloc(h->r_bytes, (size_t)c); if(!h->r_bytes) return MDK_ERR_NOMEM; h->r_capb = c; }
+    if(h->r_n == 0) h->r_off[0] = 0;
+    return 0;
+}
+static void reads_put(md_dev *h, int32_t tid, int32_t pos, uint32_t nm, uint32_t nu, const uint8_t *name, size_t nl) {
+    const int64_t i = h->r_n++;
+    h->r_contig[i] = tid; h->r_pos[i] = pos; h->r_nm[i] = (int32_t)nm; h->r_nu[i] = (int32_t)nu;
+    memcpy(h->r_bytes + h->r_nb, name, nl); h->r_nb += (int64_t)nl; h->r_off[i + 1] = h->r_nb;
+}
+int md_dev_reads_collect(md_dev *h, int slot, int64_t *n) {
+    sslot *s = slot_of(h, slot); prslot_t *q; int64_t i; int rc;
+    if(!s || !n || !h->reads_on || !h->pr || !h->pr[slot].pending) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reads_collect"); return MDK_ERR_ARG; }
+    q = &h->pr[slot]; q->pending = 0; *n = 0;
+    if((rc = reads_room(h, q->n, (int64_t)s->raw_bytes)) != 0) return rc;
+    for(i = 0; i < q->n; i++) { const uint8_t *r = s->raw + s->off[q->kept[i]] + 4; int32_t pos; memcpy(&pos, r + 4, 4); reads_put(h, s->tid, pos, q->cnt[i].nmeth, q->cnt[i].nunmeth, r + 32, strnlen((const char *)r + 32, r[8])); }
+    *n = q->n;
+    return 0;
+}
+int md_dev_reads_host(md_dev *h, int32_t tid, int64_t n, const int32_t *pos, const md_pr_count *counts, const uint64_t *name_off, const uint8_t *names) {
+    int64_t i; int rc;
+    if(!h || !h->reads_on || n < 0 || (n && (!pos || !name_off))) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reads_host"); return MDK_ERR_ARG; }
+    if(!n) return 0;
+    if((rc = reads_room(h, n, (int64_t)(name_off[n] - name_off[0]))) != 0) return rc;
+    for(i = 0; i < n; i++) reads_put(h, tid, pos[i], counts ? counts[i].nmeth : 0, counts ? counts[i].nunmeth : 0, names + name_off[i], (size_t)(name_off[i + 1] - name_off[i]));
+    return 0;
+}
+int md_dev_reads_finish(md_dev *h, md_reads_set **out) {
+    md_reads_set *r; const int64_t n = h ? h->r_n : 0;
+    if(!h || !out || !h->reads_on) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reads_finish"); return MDK_ERR_ARG; }
+    if(!(r = calloc(1, sizeof(*r)))) return MDK_ERR_NOMEM;
+    r->n = n; r->nb = h->r_nb;
+    r->contig = malloc(4 * (size_t)(n + 1)); r->pos = malloc(4 * (size_t)(n + 1)); r->nm = malloc(4 * (size_t)(n + 1)); r->nu = malloc(4 * (size_t)(n + 1)); r->off = malloc(8 * (size_t)(n + 1)); r->bytes = malloc((size_t)r->nb + 1);
+    if(n) { memcpy(r->contig, h->r_contig, 4 * (size_t)n); memcpy(r->pos, h->r_pos, 4 * (size_t)n); memcpy(r->nm, h->r_nm, 4 * (size_t)n); memcpy(r->nu, h->r_nu, 4 * (size_t)n); memcpy(r->off, h->r_off, 8 * (size_t)(n + 1)); memcpy(r->bytes, h->r_bytes, (size_t)r->nb); }
+    else r->off[0] = 0;
+    reads_drop(h);
+    *out = r;
+    return 0;
+}
+int64_t md_reads_set_count(const md_reads_set *r) { return r ? r->n : MDK_ERR_ARG; }
+int64_t md_reads_set_name_bytes(const md_reads_set *r) { return r ? r->nb : MDK_ERR_ARG; }
+int md_reads_set_copy(const md_reads_set *r, const md_reads_cols *d, int to_host) {
+    const size_t n = r ? (size_t)r->n : 0; (void)to_host;      /* ("device" memory is host memory here) */
+    if(!r || !d) return MDK_ERR_ARG;
+    if(d->contig) memcpy(d->contig, r->contig, 4 * n);
+    if(d->pos) memcpy(d->pos, r->pos, 4 * n);
+    if(d->nmeth) memcpy(d->nmeth, r->nm, 4 * n);
+    if(d->nunmeth) memcpy(d->nunmeth, r->nu, 4 * n);
+    if(d->name_off) memcpy(d->name_off, r->off, 8 * (n + 1));
+    if(d->name_bytes) memcpy(d->name_bytes, r->bytes, (size_t)r->nb);
+    return 0;
+}
+void md_reads_set_free(md_reads_set *r) { if(!r) return; free(r->contig); free(r->pos); free(r->nm); free(r->nu); free(r->off); free(r->bytes); free(r); }
