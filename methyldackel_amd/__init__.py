@@ -630,47 +630,46 @@ def run_ranks(args, n, cwd=None, env=None, command="extract", devices=None, time
 # ---- a resident extract session: the calls as tensors (include/mdk_extract.h mdk_session_*) ----
 RC_UNSUPPORTED = -23
 CALL_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("context", "uint8"), ("strand", "int8"))
+READ_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("name_offsets", "int64"), ("name_bytes", "uint8"))
 
 
 def _session_lib():
     L = lib_extract()
     if not getattr(L, "_session_types", False):
         L.mdk_session_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.mdk_session_extract.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
         L.mdk_session_close.argtypes = [C.c_void_p]
-        L.mdk_calls_count.argtypes = [C.c_void_p]
-        L.mdk_calls_count.restype = C.c_int64
-        L.mdk_calls_n_contigs.argtypes = [C.c_void_p]
-        L.mdk_calls_contig_name.argtypes = [C.c_void_p, C.c_int]
-        L.mdk_calls_contig_name.restype = C.c_char_p
-        L.mdk_calls_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.mdk_calls_free.argtypes = [C.c_void_p]
-        L.mdk_session_perread.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
-        L.mdk_reads_count.argtypes = [C.c_void_p]
-        L.mdk_reads_count.restype = C.c_int64
-        L.mdk_reads_name_bytes.argtypes = [C.c_void_p]
-        L.mdk_reads_name_bytes.restype = C.c_int64
-        L.mdk_reads_n_contigs.argtypes = [C.c_void_p]
-        L.mdk_reads_contig_name.argtypes = [C.c_void_p, C.c_int]
-        L.mdk_reads_contig_name.restype = C.c_char_p
-        L.mdk_reads_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.mdk_reads_free.argtypes = [C.c_void_p]
+        for command, kind, counts in (("extract", "calls", ("count",)), ("perread", "reads", ("count", "name_bytes"))):
+            getattr(L, f"mdk_session_{command}").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+            for f in counts:
+                getattr(L, f"mdk_{kind}_{f}").argtypes = [C.c_void_p]
+                getattr(L, f"mdk_{kind}_{f}").restype = C.c_int64
+            getattr(L, f"mdk_{kind}_n_contigs").argtypes = [C.c_void_p]
+            getattr(L, f"mdk_{kind}_contig_name").argtypes = [C.c_void_p, C.c_int]
+            getattr(L, f"mdk_{kind}_contig_name").restype = C.c_char_p
+            getattr(L, f"mdk_{kind}_copy").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            getattr(L, f"mdk_{kind}_free").argtypes = [C.c_void_p]
         L._session_types = True
     return L
 
 
-class Calls:
-    """The rows `extract` would print, as columns (one entry per call, in the order of the chunks of the schedule; within a context,
-    ascending `start`): ``contig`` (int32, index into ``contigs``, BAM header order), ``start``/``end`` (int32, bedGraph columns 2-3),
-    ``nmeth``/``nunmeth`` (int32), ``context`` (uint8: 0 CpG, 1 CHG, 2 CHH) and ``strand`` (int8: +1 C, -1 G, 0 a --mergeContext row)."""
+class _Columns:
+    """what a session run returns: ``contigs`` (names, BAM header order) and one tensor attribute per entry of COLUMNS"""
+    COLUMNS = ()
 
     def __init__(self, contigs, columns):
         self.contigs = contigs
-        for name, _ in CALL_COLUMNS:
+        for name, _ in self.COLUMNS:
             setattr(self, name, columns[name])
 
     def __len__(self):
-        return int(self.start.shape[0])
+        return int(self.contig.shape[0])
+
+
+class Calls(_Columns):
+    """The rows `extract` would print, as columns (one entry per call, in the order of the chunks of the schedule; within a context,
+    ascending `start`): ``contig`` (int32, index into ``contigs``, BAM header order), ``start``/``end`` (int32, bedGraph columns 2-3),
+    ``nmeth``/``nunmeth`` (int32), ``context`` (uint8: 0 CpG, 1 CHG, 2 CHH) and ``strand`` (int8: +1 C, -1 G, 0 a --mergeContext row)."""
+    COLUMNS = CALL_COLUMNS
 
     def rows(self, context=None):
         """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
@@ -678,22 +677,12 @@ class Calls:
         return [(self.contigs[c], a, b, m, u) for c, a, b, m, u, x in zip(*cols) if context is None or x == context]
 
 
-READ_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("name_offsets", "int64"), ("name_bytes", "uint8"))
-
-
-class Reads:
+class Reads(_Columns):
     """The lines `perRead` would print, as columns (one row per line, in the command's order: chunks of the schedule, reads of a chunk in
     file order): ``contig`` (int32, index into ``contigs``), ``pos`` (int32, the line's column 3), ``nmeth``/``nunmeth`` (int32: the line
     prints 100*nmeth/(nmeth+nunmeth) and the sum), ``name_offsets`` (int64, len + 1 entries, the first 0) and ``name_bytes`` (uint8, the read
     names packed without separators: name i is name_bytes[name_offsets[i]:name_offsets[i + 1]])."""
-
-    def __init__(self, contigs, columns):
-        self.contigs = contigs
-        for name, _ in READ_COLUMNS:
-            setattr(self, name, columns[name])
-
-    def __len__(self):
-        return int(self.pos.shape[0])
+    COLUMNS = READ_COLUMNS
 
     def names(self):
         """the read names on the host, as str"""
@@ -723,60 +712,43 @@ class Session:
             raise _rc_error("mdk_session_open", rc)
         self._h = h
 
-    def extract(self, args, device_tensors: bool = True) -> Calls:
+    def _run(self, command, kind, result, args, device_tensors):
+        """one run of `command` on the handle: its mdk_<kind> object copied, column by column, into tensors -- device to device into
+        tensors torch allocated on the session's device, or into CPU tensors -- and freed"""
         import torch
         if self._h is None:
             raise MdkError("the session is closed")
-        argv = ["extract"] + [str(a) for a in args]
-        arr = (C.c_char_p * (len(argv) + 1))(*[a.encode() for a in argv], None)
+        L = self._L
+        argv = [command] + [str(a) for a in args]
+        arr = (C.c_char_p * (len(argv) + 1))(*[os.fsencode(a) for a in argv], None)
         out = C.c_void_p()
-        rc = self._L.mdk_session_extract(self._h, len(argv), arr, C.byref(out))
+        rc = getattr(L, f"mdk_session_{command.lower()}")(self._h, len(argv), arr, C.byref(out))
         if rc:
-            raise _rc_error("extract", rc)
+            raise _rc_error(command, rc)
         try:
-            n = int(self._L.mdk_calls_count(out))
-            contigs = [self._L.mdk_calls_contig_name(out, i).decode() for i in range(self._L.mdk_calls_n_contigs(out))]
+            n = int(getattr(L, f"mdk_{kind}_count")(out))
+            size = {"name_offsets": n + 1, "name_bytes": int(L.mdk_reads_name_bytes(out)) if kind == "reads" else 0}      # every other column: n
+            contigs = [getattr(L, f"mdk_{kind}_contig_name")(out, i).decode() for i in range(getattr(L, f"mdk_{kind}_n_contigs")(out))]
             dev = torch.device("cuda", self.device) if device_tensors else torch.device("cpu")
             cols = {}
-            for k, (name, dt) in enumerate(CALL_COLUMNS):
-                t = torch.empty(n, dtype=getattr(torch, dt), device=dev)
-                if n:
-                    rc = self._L.mdk_calls_copy(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
+            for k, (name, dt) in enumerate(result.COLUMNS):
+                t = (torch.empty if n else torch.zeros)(size.get(name, n), dtype=getattr(torch, dt), device=dev)
+                if n and t.numel():
+                    rc = getattr(L, f"mdk_{kind}_copy")(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
                     if rc:
                         raise _rc_error(f"copying the {name} column", rc)
                 cols[name] = t
         finally:
-            self._L.mdk_calls_free(out)
-        return Calls(contigs, cols)
+            getattr(L, f"mdk_{kind}_free")(out)
+        return result(contigs, cols)
+
+    def extract(self, args, device_tensors: bool = True) -> Calls:
+        return self._run("extract", "calls", Calls, args, device_tensors)
 
     def perread(self, args, device_tensors: bool = True) -> Reads:
         """The `perRead` command line (without the command name) on the same handle: the rows it would print, as Reads.  -o is ignored;
         any non-zero return code raises MdkError with ``.rc``.  Extract and perRead runs may alternate on one session."""
-        import torch
-        if self._h is None:
-            raise MdkError("the session is closed")
-        argv = ["perRead"] + [str(a) for a in args]
-        arr = (C.c_char_p * (len(argv) + 1))(*[os.fsencode(a) for a in argv], None)
-        out = C.c_void_p()
-        rc = self._L.mdk_session_perread(self._h, len(argv), arr, C.byref(out))
-        if rc:
-            raise _rc_error("perRead", rc)
-        try:
-            n, nb = int(self._L.mdk_reads_count(out)), int(self._L.mdk_reads_name_bytes(out))
-            contigs = [self._L.mdk_reads_contig_name(out, i).decode() for i in range(self._L.mdk_reads_n_contigs(out))]
-            dev = torch.device("cuda", self.device) if device_tensors else torch.device("cpu")
-            cols = {}
-            for k, (name, dt) in enumerate(READ_COLUMNS):
-                size = n + 1 if name == "name_offsets" else nb if name == "name_bytes" else n
-                t = torch.zeros(size, dtype=getattr(torch, dt), device=dev) if n == 0 else torch.empty(size, dtype=getattr(torch, dt), device=dev)
-                if n and size:
-                    rc = self._L.mdk_reads_copy(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
-                    if rc:
-                        raise _rc_error(f"copying the {name} column", rc)
-                cols[name] = t
-        finally:
-            self._L.mdk_reads_free(out)
-        return Reads(contigs, cols)
+        return self._run("perRead", "reads", Reads, args, device_tensors)
 
     def close(self):
         if self._h is not None:

@@ -138,12 +138,10 @@ static int perread_reads_host(mdk_plan *p, md_dev *dev, const mdk_chunk *c, cons
     return rc;
 }
 
-struct mdk_reads { md_reads_set *set; int64_t n, n_bytes; int n_contigs; char **names; };
-
 /* perRead_main's loop; S != NULL: a session's run -- no text, every chunk's rows kept on S's device handle (opened at the first run of the
  * session, reset before every later one) and handed over in *out */
-static int perread_run(int argc, char *argv[], mdk_session *S, mdk_reads **out) {
-    mdk_plan *p = NULL; md_dev *dev = NULL; mdk_chunk ch[2]; int have[2] = {0, 0}; int rc, k = 0, ret = 0, more = 1, i; devopen_t dop; pthread_t dth; int dth_ok;
+static int perread_run(int argc, char *argv[], mdk_session *S, void **out) {
+    mdk_plan *p = NULL; md_dev *dev = NULL; mdk_chunk ch[2]; int have[2] = {0, 0}; int rc, k = 0, ret = 0, more = 1; devopen_t dop; pthread_t dth; int dth_ok;
     int slot[2] = {0, 1};
     if(argc > 2 && !S) hip_warm_up();
     rc = perread_open(argc, argv, &p, S != NULL);
@@ -225,13 +223,8 @@ static int perread_run(int argc, char *argv[], mdk_session *S, mdk_reads **out) 
         md_reads_set *set = NULL; int frc;
         (void)md_dev_sync(dev);          /* (after an error a chunk may still be reading the plan's memory) */
         frc = md_dev_reads_finish(dev, &set);
-        if(!ret && frc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; }
-        if(!ret) {
-            mdk_reads *r = calloc(1, sizeof(*r)); const int nt = p->bam->n_targets;
-            if(r) r->names = calloc((size_t)nt + 1, sizeof(char *));
-            if(!r || !r->names) { free(r); md_reads_set_free(set); ret = -5; }
-            else { r->set = set; r->n = md_reads_set_count(set); r->n_bytes = md_reads_set_name_bytes(set); r->n_contigs = nt; for(i = 0; i < nt; i++) r->names[i] = strdup(p->bam->target_name[i]); *out = r; }
-        } else md_reads_set_free(set);
+        ret = session_result(ret, frc, p, sizeof(mdk_reads), set, md_reads_set_count(set), out);
+        if(ret) md_reads_set_free(set); else ((mdk_reads *)*out)->n_bytes = md_reads_set_name_bytes(set);
     }
     mdk_plan_close(p);
     return ret;
@@ -240,22 +233,15 @@ static int perread_run(int argc, char *argv[], mdk_session *S, mdk_reads **out) 
 int perRead_main(int argc, char *argv[]) { return perread_run(argc, argv, NULL, NULL); }
 
 /* ---- the session's perRead (include/mdk_extract.h) ---- */
-int mdk_session_perread(mdk_session *s, int argc, char *argv[], mdk_reads **out) {
-    int rc;
-    if(!s || !out || argc < 1 || !argv) return MDK_ERR_ARG;
-    *out = NULL;
-    rc = perread_run(argc, argv, s, out);
-    if(rc == 0 && !*out) { *out = calloc(1, sizeof(mdk_reads)); if(!*out) return -5; }      /* (help / version: no run, no reads) */
-    return rc;
-}
-int64_t mdk_reads_count(const mdk_reads *r) { return r ? r->n : -1; }
+int mdk_session_perread(mdk_session *s, int argc, char *argv[], mdk_reads **out) { return session_run(s, argc, argv, (void **)out, sizeof(mdk_reads), perread_run); }
+int64_t mdk_reads_count(const mdk_reads *r) { return r ? r->r.n : -1; }
 int64_t mdk_reads_name_bytes(const mdk_reads *r) { return r ? r->n_bytes : -1; }
-int mdk_reads_n_contigs(const mdk_reads *r) { return r ? r->n_contigs : -1; }
-const char *mdk_reads_contig_name(const mdk_reads *r, int i) { return (r && i >= 0 && i < r->n_contigs) ? r->names[i] : NULL; }
+int mdk_reads_n_contigs(const mdk_reads *r) { return result_n_contigs(r ? &r->r : NULL); }
+const char *mdk_reads_contig_name(const mdk_reads *r, int i) { return result_contig_name(r ? &r->r : NULL, i); }
 int mdk_reads_copy(const mdk_reads *r, int column, void *dst, int to_host) {
     md_reads_cols d; memset(&d, 0, sizeof(d));
     if(!r || !dst || column < 0 || column > MDK_READS_NAME_BYTES) return MDK_ERR_ARG;
-    if(!r->set) { if(column == MDK_READS_NAME_OFFSETS) { const int64_t z = 0; if(to_host) memcpy(dst, &z, sizeof(z)); else return MDK_ERR_ARG; } return 0; }     /* (an empty result without a run: one offset, 0) */
+    if(!r->r.set) { if(column == MDK_READS_NAME_OFFSETS) { const int64_t z = 0; if(to_host) memcpy(dst, &z, sizeof(z)); else return MDK_ERR_ARG; } return 0; }     /* (an empty result without a run: one offset, 0) */
     switch(column) {
     case MDK_READS_CONTIG: d.contig = dst; break;
     case MDK_READS_POS: d.pos = dst; break;
@@ -264,12 +250,6 @@ int mdk_reads_copy(const mdk_reads *r, int column, void *dst, int to_host) {
     case MDK_READS_NAME_OFFSETS: d.name_off = dst; break;
     default: d.name_bytes = dst; break;
     }
-    return md_reads_set_copy(r->set, &d, to_host);
+    return md_reads_set_copy(r->r.set, &d, to_host);
 }
-void mdk_reads_free(mdk_reads *r) {
-    int i;
-    if(!r) return;
-    md_reads_set_free(r->set);
-    for(i = 0; i < r->n_contigs; i++) free(r->names[i]);
-    free(r->names); free(r);
-}
+void mdk_reads_free(mdk_reads *r) { if(r) { md_reads_set_free(r->r.set); session_result_free(&r->r); } }

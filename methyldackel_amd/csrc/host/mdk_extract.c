@@ -216,8 +216,7 @@ static void xopen_start(mdk_plan *p, void *arg) {
     o->started = pthread_create(&o->th, NULL, devopen_main, &o->d) == 0;
 }
 
-/* ---- a resident session (include/mdk_extract.h): the same pipeline, one device handle across runs, calls kept on the device ---- */
-struct mdk_calls { md_calls_set *set; int64_t n; int n_contigs; char **names; };
+/* ---- a resident session (include/mdk_extract.h, mdk_session.c): the same pipeline, one device handle across runs, calls kept on the device ---- */
 /* the session's after_options: options that only shape text or files are refused; the device configuration is worked out as for the command */
 static void session_options(mdk_plan *p, void *arg) {
     xopen *o = arg; const opts_t *q = &p->o;
@@ -234,17 +233,10 @@ MDK_LOCAL void session_geometry(md_dev_cfg *cfg) {
     else g_ngroups = 3;
     cfg->n_slots = MDK_NGROUPS * MDK_GROUP; cfg->n_streams = MDK_NGROUPS;
 }
-MDK_LOCAL void session_device(mdk_session *S, devopen_t *d) {
-    d->device = S->device;
-    if(S->dev && (S->cfg.n_slots != d->cfg.n_slots || S->cfg.n_streams != d->cfg.n_streams)) { md_dev_close(S->dev); S->dev = NULL; }
-    if(S->dev) { d->rc = md_dev_reset(S->dev, &d->cfg); d->dev = S->dev; if(d->rc) { snprintf(d->err, sizeof(d->err), "%s", md_dev_last_error()); md_dev_close(S->dev); S->dev = d->dev = NULL; } }
-    else devopen_main(d);
-    S->dev = d->dev; S->cfg = d->cfg;
-}
 
 /* extract_main's pipeline; S != NULL: a session's run -- no output files, no emitter, every collected group compacted into calls on S's device
  * handle (opened at the first run, reset before every later one), handed over in *out */
-static int extract_run(int argc, char *argv[], mdk_session *S, mdk_calls **out) {
+static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
     mdk_plan *p = NULL; md_dev *dev = NULL; xpipe *X = NULL; int rc, ret = 0, more = 1, i, g_i; xopen dop; pthread_t cth, rth, preg; int cth_ok = 0, rth_ok = 0, preg_ok = 0; emitter em;
     double T0 = now_s(), t_open, t_dev, w_next = 0, w_sub = 0, w_group = 0, w_ref = 0, w_rel = 0, ta; uint64_t n_chunks = 0; int32_t ref_t0, ref_t1;
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] entered at epoch %.3f\n", ts.tv_sec + 1e-9 * ts.tv_nsec); }
@@ -359,13 +351,8 @@ static int extract_run(int argc, char *argv[], mdk_session *S, mdk_calls **out) 
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] plan open %.3fs, device ready at %.3fs, uploader: wait-for-chunk %.3fs wait-for-reference %.3fs wait-for-group %.3fs submit %.3fs wait-for-uploads %.3fs; collector: download %.3fs emit %.3fs, total %.3fs; chunks prepared on the host after all: %d\n", t_open, t_dev, w_next, w_ref, w_group, w_sub, w_rel, X->w_down, X->w_emit, now_s() - T0, X->n_host_prep);
     if(S) {          /* the rows, in schedule order, handed over with the contig names; the handle's calls state is finished either way */
         md_calls_set *set = NULL; const int frc = md_dev_calls_finish(dev, &set);
-        if(!ret && frc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; }
-        if(!ret) {
-            mdk_calls *c = calloc(1, sizeof(*c)); const int nt = p->bam->n_targets;
-            if(c) c->names = calloc((size_t)nt + 1, sizeof(char *));
-            if(!c || !c->names) { free(c); md_calls_set_free(set); ret = -5; }
-            else { c->set = set; c->n = md_calls_set_count(set); c->n_contigs = nt; for(i = 0; i < nt; i++) c->names[i] = strdup(p->bam->target_name[i]); *out = c; }
-        } else md_calls_set_free(set);
+        ret = session_result(ret, frc, p, sizeof(mdk_calls), set, md_calls_set_count(set), out);
+        if(ret) md_calls_set_free(set);
     } else if(ret == 0) mdk_plan_finish(p);
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] leaving at epoch %.3f (resident %.0f MB, of which file-backed/shared %.0f MB)\n", ts.tv_sec + 1e-9 * ts.tv_nsec, rss_mb(0), rss_mb(1)); }
     if(!S && fast_exit_wanted()) leave_fast_plan(p, ret);
@@ -384,31 +371,14 @@ int extract_main(int argc, char *argv[]) {
     return extract_run(argc, argv, NULL, NULL);
 }
 
-int mdk_session_open(int device, mdk_session **out) {
-    mdk_session *s;
-    if(!out || device < 0) return MDK_ERR_ARG;
-    *out = NULL;
-    if(!(s = calloc(1, sizeof(*s)))) return -5;
-    s->device = device;
-    *out = s;
-    return 0;
-}
-int mdk_session_extract(mdk_session *s, int argc, char *argv[], mdk_calls **out) {
-    int rc;
-    if(!s || !out || argc < 1 || !argv) return MDK_ERR_ARG;
-    *out = NULL;
-    rc = extract_run(argc, argv, s, out);
-    if(rc == 0 && !*out) { *out = calloc(1, sizeof(mdk_calls)); if(!*out) return -5; }      /* (help / version: no run, no calls) */
-    return rc;
-}
-void mdk_session_close(mdk_session *s) { if(!s) return; if(s->dev) md_dev_close(s->dev); free(s); }
-int64_t mdk_calls_count(const mdk_calls *c) { return c ? c->n : -1; }
-int mdk_calls_n_contigs(const mdk_calls *c) { return c ? c->n_contigs : -1; }
-const char *mdk_calls_contig_name(const mdk_calls *c, int i) { return (c && i >= 0 && i < c->n_contigs) ? c->names[i] : NULL; }
+int mdk_session_extract(mdk_session *s, int argc, char *argv[], mdk_calls **out) { return session_run(s, argc, argv, (void **)out, sizeof(mdk_calls), extract_run); }
+int64_t mdk_calls_count(const mdk_calls *c) { return c ? c->r.n : -1; }
+int mdk_calls_n_contigs(const mdk_calls *c) { return result_n_contigs(c ? &c->r : NULL); }
+const char *mdk_calls_contig_name(const mdk_calls *c, int i) { return result_contig_name(c ? &c->r : NULL, i); }
 int mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host) {
     md_calls_cols d; memset(&d, 0, sizeof(d));
     if(!c || !dst || column < 0 || column > MDK_CALLS_STRAND) return MDK_ERR_ARG;
-    if(!c->set || c->n == 0) return 0;
+    if(!c->r.set || c->r.n == 0) return 0;
     switch(column) {
     case MDK_CALLS_CONTIG: d.contig = dst; break;
     case MDK_CALLS_START: d.start = dst; break;
@@ -418,12 +388,6 @@ int mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host) {
     case MDK_CALLS_CONTEXT: d.context = dst; break;
     default: d.strand = dst; break;
     }
-    return md_calls_set_copy(c->set, &d, to_host);
+    return md_calls_set_copy(c->r.set, &d, to_host);
 }
-void mdk_calls_free(mdk_calls *c) {
-    int i;
-    if(!c) return;
-    md_calls_set_free(c->set);
-    for(i = 0; i < c->n_contigs; i++) free(c->names[i]);
-    free(c->names); free(c);
-}
+void mdk_calls_free(mdk_calls *c) { if(c) { md_calls_set_free(c->r.set); session_result_free(&c->r); } }

@@ -3,6 +3,7 @@
  *   mdk_pipeline.c   per-record work (admission, strand, pairing, CIGAR expansion) and the reader/worker chunk pipeline
  *   mdk_emit.c       text post-pass and the ordered multi-threaded emitter
  *   mdk_extract.c    extract_main (the drop-in entry point) and the process-level helpers of the commands
+ *   mdk_session.c    the resident session's handle and the result object of its runs
  *   mdk_cmd_mbias.c, mdk_cmd_perread.c, mdk_mbias.c, mdk_mergecontext.c   the other commands
  * Nothing here is part of the C ABI. */
 #ifndef MDK_PLAN_H
@@ -136,10 +137,23 @@ typedef struct {
 
 /* opening the device on its own thread while the host pipeline is already running (mdk_extract.c) */
 typedef struct { int device; md_dev_cfg cfg; md_dev *dev; int rc; char err[512]; } devopen_t;
-/* a resident session (include/mdk_extract.h): one device handle across the runs of every command it serves (mdk_extract.c, mdk_cmd_perread.c) */
+/* a resident session (include/mdk_extract.h): one device handle across the runs of every command it serves (mdk_session.c; the runs
+ * themselves: mdk_extract.c, mdk_cmd_perread.c) */
 struct mdk_session { int device; md_dev *dev; md_dev_cfg cfg; };
-MDK_LOCAL void session_geometry(md_dev_cfg *cfg);              /* the slots and streams of every session run, whatever its command: switching commands resets the handle */
+MDK_LOCAL void session_geometry(md_dev_cfg *cfg);              /* (mdk_extract.c) the slots and streams of every session run, whatever its command: switching commands resets the handle */
 MDK_LOCAL void session_device(mdk_session *S, devopen_t *d);   /* the session's handle for a run with d->cfg: opened at the first run, reset before every later one */
+/* what a session run hands back, whatever its command (mdk_session.c): the rows' device set, their count, the contig names of the BAM header */
+typedef struct { void *set; int64_t n; int n_contigs; char **names; } mdk_result;
+struct mdk_calls { mdk_result r; };
+struct mdk_reads { mdk_result r; int64_t n_bytes; };
+typedef int (*session_run_fn)(int argc, char *argv[], mdk_session *S, void **out);
+MDK_LOCAL int session_run(mdk_session *s, int argc, char *argv[], void **out, size_t size, session_run_fn run);     /* mdk_session_<command>: argument check, the run, an empty result of `size` bytes where it made none */
+/* the end of a run: `ret` its code so far, `frc` what md_dev_{calls,reads}_finish gave.  *out = a new result of `size` bytes (an mdk_result first) that owns
+ * `set` and copies of p's contig names; returns the run's code, and where that is not 0 the set is still the caller's to free */
+MDK_LOCAL int session_result(int ret, int frc, const mdk_plan *p, size_t size, void *set, int64_t n, void **out);
+MDK_LOCAL void session_result_free(mdk_result *r);             /* the names and the object (the set goes first, by its own free) */
+MDK_LOCAL int result_n_contigs(const mdk_result *r);
+MDK_LOCAL const char *result_contig_name(const mdk_result *r, int i);
 
 MDK_LOCAL void plan_free(mdk_plan *p);
 MDK_LOCAL int plan_open_ex(int argc, char *argv[], mdk_plan **out, void (*after_options)(mdk_plan *, void *), void *ctx);

@@ -16,22 +16,22 @@
 
 struct CallsTile { uint64_t src; uint32_t n, pad; };              // rows of a tile: arena index of the first, count (written by the kernel)
 struct CallsChunk { uint32_t key; int32_t tid; uint64_t tile0; int32_t ntiles; };    // a compacted chunk: its tiles are tiles[tile0 .. tile0 + ntiles)
+// columns of the row arena, of the tile table and of a result set (md_calls_cols' order)
+enum { A_START = 0, A_END, A_NM, A_NU, A_CTX, A_STRAND };
+static const ColSpec ARENA_COLS[] = {{4, 0}, {4, 0}, {4, 0}, {4, 0}, {1, 0}, {1, 0}};
+static const ColSpec TILE_COLS[] = {{sizeof(CallsTile), 0}};
+enum { R_CONTIG = 0, R_START, R_END, R_NM, R_NU, R_CTX, R_STRAND };
+static const ColSpec SET_COLS[] = {{4, 0}, {4, 0}, {4, 0}, {4, 0}, {4, 0}, {1, 0}, {1, 0}};
 struct CallsState {
     md_calls_cfg cfg; bool on = false;
-    hipStream_t st = nullptr; hipEvent_t done = nullptr;     // the compactions run here; `done` orders the slots' streams after them
-    // row arena (columns) and tile table: plain hipMalloc, grown by doubling, kept across runs
-    int32_t *start = nullptr, *end = nullptr, *nm = nullptr, *nu = nullptr; uint8_t *ctx = nullptr; int8_t *strand = nullptr;
-    uint64_t cap_rows = 0, used_rows = 0;
-    CallsTile *tiles = nullptr; uint64_t cap_tiles = 0, used_tiles = 0;
+    TableLane lane;                                          // the compactions run here
+    ColTable rows{ARENA_COLS, 6, "hipMalloc(call arena)"}; uint64_t used_rows = 0;       // kept across runs
+    ColTable tiles{TILE_COLS, 1, "hipMalloc(call tiles)"}; uint64_t used_tiles = 0;
     uint32_t *d_err = nullptr;
     std::vector<CallsChunk> chunks;
 };
 
-struct md_calls_set {
-    int device = 0; int64_t n = 0;
-    int32_t *contig = nullptr, *start = nullptr, *end = nullptr, *nm = nullptr, *nu = nullptr; uint8_t *ctx = nullptr; int8_t *strand = nullptr;
-    void *mem = nullptr;
-};
+struct md_calls_set { int device = 0; int64_t n = 0; ColTable cols{SET_COLS, 7, "hipMalloc(calls)"}; };
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -159,54 +159,11 @@ __global__ __launch_bounds__(CALLS_WG) void k_calls_gather(const KGather G) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static void calls_free_arena(CallsState *c) {
-    for(void *p : {(void *)c->start, (void *)c->end, (void *)c->nm, (void *)c->nu, (void *)c->ctx, (void *)c->strand}) if(p) (void)hipFree(p);
-    c->start = c->end = c->nm = c->nu = nullptr; c->ctx = nullptr; c->strand = nullptr; c->cap_rows = 0;
-}
-// room for `rows` more rows and `tiles` more tiles.  Growing copies what is there: every compaction queued so far is waited for first.
-static int calls_reserve(CallsState *c, uint64_t rows, uint64_t tiles) {
-    if(c->used_rows + rows > c->cap_rows) {
-        uint64_t want = std::max<uint64_t>(c->cap_rows * 2, std::max<uint64_t>(c->used_rows + rows, 1u << 20));
-        HIPCHK(hipStreamSynchronize(c->st));
-        int32_t *s = nullptr, *e = nullptr, *m = nullptr, *u = nullptr; uint8_t *x = nullptr; int8_t *y = nullptr;
-        hipError_t r = hipMalloc((void **)&s, want * 4);
-        if(r == hipSuccess) r = hipMalloc((void **)&e, want * 4);
-        if(r == hipSuccess) r = hipMalloc((void **)&m, want * 4);
-        if(r == hipSuccess) r = hipMalloc((void **)&u, want * 4);
-        if(r == hipSuccess) r = hipMalloc((void **)&x, want);
-        if(r == hipSuccess) r = hipMalloc((void **)&y, want);
-        if(r != hipSuccess) { for(void *p : {(void *)s, (void *)e, (void *)m, (void *)u, (void *)x, (void *)y}) if(p) (void)hipFree(p); return fail(MDK_ERR_NOMEM, "hipMalloc(call arena)", r); }
-        if(c->used_rows) {
-            const size_t n = (size_t)c->used_rows;
-            HIPCHK(hipMemcpyAsync(s, c->start, n * 4, hipMemcpyDeviceToDevice, c->st)); HIPCHK(hipMemcpyAsync(e, c->end, n * 4, hipMemcpyDeviceToDevice, c->st));
-            HIPCHK(hipMemcpyAsync(m, c->nm, n * 4, hipMemcpyDeviceToDevice, c->st)); HIPCHK(hipMemcpyAsync(u, c->nu, n * 4, hipMemcpyDeviceToDevice, c->st));
-            HIPCHK(hipMemcpyAsync(x, c->ctx, n, hipMemcpyDeviceToDevice, c->st)); HIPCHK(hipMemcpyAsync(y, c->strand, n, hipMemcpyDeviceToDevice, c->st));
-            HIPCHK(hipStreamSynchronize(c->st));
-        }
-        calls_free_arena(c);
-        c->start = s; c->end = e; c->nm = m; c->nu = u; c->ctx = x; c->strand = y; c->cap_rows = want;
-    }
-    if(c->used_tiles + tiles > c->cap_tiles) {
-        uint64_t want = std::max<uint64_t>(c->cap_tiles * 2, std::max<uint64_t>(c->used_tiles + tiles, 1u << 14));
-        HIPCHK(hipStreamSynchronize(c->st));
-        CallsTile *t = nullptr;
-        hipError_t r = hipMalloc((void **)&t, want * sizeof(CallsTile));
-        if(r != hipSuccess) return fail(MDK_ERR_NOMEM, "hipMalloc(call tiles)", r);
-        if(c->used_tiles) { r = hipMemcpy(t, c->tiles, (size_t)c->used_tiles * sizeof(CallsTile), hipMemcpyDeviceToDevice); if(r != hipSuccess) { (void)hipFree(t); return fail(MDK_ERR_HIP, "hipMemcpy(call tiles)", r); } }
-        if(c->tiles) (void)hipFree(c->tiles);
-        c->tiles = t; c->cap_tiles = want;
-    }
-    return 0;
-}
-
 void calls_state_free(md_dev *h) {
     CallsState *c = h->calls; if(!c) return;
-    if(c->st) (void)hipStreamSynchronize(c->st);
-    calls_free_arena(c);
-    if(c->tiles) (void)hipFree(c->tiles);
+    c->lane.close();
+    c->rows.release(); c->tiles.release();
     if(c->d_err) (void)hipFree(c->d_err);
-    if(c->done) (void)hipEventDestroy(c->done);
-    if(c->st) (void)hipStreamDestroy(c->st);
     delete c; h->calls = nullptr;
 }
 
@@ -215,11 +172,9 @@ extern "C" int md_dev_calls_begin(md_dev *h, const md_calls_cfg *cfg) {
     HIPCHK(hipSetDevice(h->device));
     if(!h->calls) h->calls = new CallsState();
     CallsState *c = h->calls;
-    if(!c->st) { c->st = mdk_stream_take(h->device); if(!c->st) return fail(MDK_ERR_HIP, "hipStreamCreateWithFlags", hipGetLastError()); }
-    if(!c->done) HIPCHK(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
+    { const int rc = c->lane.open(h->device); if(rc) return rc; }
     if(!c->d_err) HIPCHK(hipMalloc((void **)&c->d_err, sizeof(uint32_t)));
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->st));
+    HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->lane.st));
     c->cfg = *cfg; c->on = true; c->used_rows = 0; c->used_tiles = 0; c->chunks.clear();
     h->no_pack = true;            // group launches stop copying their sites to pinned host memory: nobody downloads them
     return 0;
@@ -247,11 +202,13 @@ extern "C" int md_dev_calls_group(md_dev *h, const int *slots, const uint32_t *k
     for(int i = 0; i < n; i++) if(!rcs[i]) HIPCHK(hipStreamSynchronize(ss[i]->run ? ss[i]->run : ss[i]->stream));     // (a chunk prepared and piled up again inside finish_eval)
     uint64_t rows = 0, tiles = 0;
     for(int i = 0; i < n; i++) if(!rcs[i]) { rows += (uint64_t)cnt[i]; tiles += (uint64_t)std::max(ss[i]->ntiles, 0); }
-    { const int rc = calls_reserve(c, rows, tiles); if(rc) return rc; }
+    // room for the group's rows and tiles (growing copies what is there, behind every compaction queued so far)
+    { int rc = c->rows.reserve(c->used_rows, rows, CALLS_ROWS_FLOOR, c->lane.st); if(!rc) rc = c->tiles.reserve(c->used_tiles, tiles, CALLS_TILES_FLOOR, c->lane.st); if(rc) return rc; }
     KCalls K; memset(&K, 0, sizeof(K));
     K.min_depth = c->cfg.min_depth; K.merge = c->cfg.merge; K.min_opp = c->cfg.min_opposite_depth; K.max_vf = c->cfg.max_variant_frac;
     K.ctx_mask = (c->cfg.ctx_on[0] ? 1 : 0) | (c->cfg.ctx_on[1] ? 2 : 0) | (c->cfg.ctx_on[2] ? 4 : 0);
-    K.start = c->start; K.end = c->end; K.nm = c->nm; K.nu = c->nu; K.ctx = c->ctx; K.strand = c->strand; K.tiles = c->tiles; K.err = c->d_err;
+    K.start = c->rows.col<int32_t>(A_START); K.end = c->rows.col<int32_t>(A_END); K.nm = c->rows.col<int32_t>(A_NM); K.nu = c->rows.col<int32_t>(A_NU);
+    K.ctx = c->rows.col<uint8_t>(A_CTX); K.strand = c->rows.col<int8_t>(A_STRAND); K.tiles = c->tiles.col<CallsTile>(0); K.err = c->d_err;
     int total = 0;
     for(int i = 0; i < n; i++) {
         Slot *s = ss[i];
@@ -270,15 +227,11 @@ extern "C" int md_dev_calls_group(md_dev *h, const int *slots, const uint32_t *k
     }
     K.tstart[K.n] = total;
     if(total > 0) {
-        hipLaunchKernelGGL(k_calls_compact, dim3((unsigned)total), dim3(CALLS_WG), 0, c->st, K);
+        hipLaunchKernelGGL(k_calls_compact, dim3((unsigned)total), dim3(CALLS_WG), 0, c->lane.st, K);
         HIPCHK(hipGetLastError());
     }
     // the slots' next uploads and launches come after the compaction has read their sites
-    HIPCHK(hipEventRecord(c->done, c->st));
-    for(int i = 0; i < n; i++) {
-        HIPCHK(hipStreamWaitEvent(ss[i]->stream, c->done, 0));
-        if(ss[i]->run && ss[i]->run != ss[i]->stream) HIPCHK(hipStreamWaitEvent(ss[i]->run, c->done, 0));
-    }
+    { const int rc = c->lane.fence(ss, n); if(rc) return rc; }
     for(int i = 0; i < n; i++) ss[i]->busy = false;
     return 0;
 }
@@ -288,12 +241,13 @@ extern "C" int md_dev_calls_finish(md_dev *h, md_calls_set **out) {
     *out = nullptr;
     HIPCHK(hipSetDevice(h->device));
     CallsState *c = h->calls;
-    HIPCHK(hipStreamSynchronize(c->st));
+    hipStream_t st = c->lane.st;
+    HIPCHK(hipStreamSynchronize(st));
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, c->d_err, sizeof(err), hipMemcpyDeviceToHost));
     if(err) return fail(MDK_ERR_ARG, "md_dev_calls_finish: inconsistent tile segments", hipSuccess);
     std::vector<CallsTile> tt((size_t)c->used_tiles);
-    if(c->used_tiles) HIPCHK(hipMemcpy(tt.data(), c->tiles, sizeof(CallsTile) * (size_t)c->used_tiles, hipMemcpyDeviceToHost));
+    if(c->used_tiles) { const int rc = c->tiles.copy_out(0, c->used_tiles, tt.data(), hipMemcpyDeviceToHost); if(rc) return rc; }
     std::vector<CallsChunk> ch = c->chunks;
     std::stable_sort(ch.begin(), ch.end(), [](const CallsChunk &a, const CallsChunk &b) { return a.key < b.key; });
     std::vector<GatherEnt> ge; uint64_t n = 0;
@@ -305,27 +259,25 @@ extern "C" int md_dev_calls_finish(md_dev *h, md_calls_set **out) {
             GatherEnt g; g.src = e.src; g.dst = n; g.n = e.n; g.tid = k.tid; ge.push_back(g); n += e.n;
         }
     md_calls_set *r = new md_calls_set(); r->device = h->device; r->n = (int64_t)n;
-    const size_t cap = (size_t)n + 64, a4 = (cap * 4 + 255) & ~(size_t)255, a1 = (cap + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&r->mem, 5 * a4 + 2 * a1);
-    if(e != hipSuccess) { delete r; return fail(MDK_ERR_NOMEM, "hipMalloc(calls)", e); }
-    char *m = (char *)r->mem;
-    r->contig = (int32_t *)m; r->start = (int32_t *)(m + a4); r->end = (int32_t *)(m + 2 * a4); r->nm = (int32_t *)(m + 3 * a4); r->nu = (int32_t *)(m + 4 * a4);
-    r->ctx = (uint8_t *)(m + 5 * a4); r->strand = (int8_t *)(m + 5 * a4 + a1);
+    { const int rc = r->cols.reserve(0, n + 64, 0, st); if(rc) { delete r; return rc; } }
     if(!ge.empty()) {
         GatherEnt *d_ge = nullptr;
-        e = hipMalloc((void **)&d_ge, sizeof(GatherEnt) * ge.size());
-        if(e == hipSuccess) e = hipMemcpyAsync(d_ge, ge.data(), sizeof(GatherEnt) * ge.size(), hipMemcpyHostToDevice, c->st);
+        hipError_t e = hipMalloc((void **)&d_ge, sizeof(GatherEnt) * ge.size());
+        if(e == hipSuccess) e = hipMemcpyAsync(d_ge, ge.data(), sizeof(GatherEnt) * ge.size(), hipMemcpyHostToDevice, st);
         if(e == hipSuccess) {
+            const ColTable &a = c->rows, &o = r->cols;
             KGather G; G.ent = d_ge; G.n_ent = ge.size();
-            G.start = c->start; G.end = c->end; G.nm = c->nm; G.nu = c->nu; G.ctx = c->ctx; G.strand = c->strand;
-            G.o_contig = r->contig; G.o_start = r->start; G.o_end = r->end; G.o_nm = r->nm; G.o_nu = r->nu; G.o_ctx = r->ctx; G.o_strand = r->strand;
+            G.start = a.col<int32_t>(A_START); G.end = a.col<int32_t>(A_END); G.nm = a.col<int32_t>(A_NM); G.nu = a.col<int32_t>(A_NU);
+            G.ctx = a.col<uint8_t>(A_CTX); G.strand = a.col<int8_t>(A_STRAND);
+            G.o_contig = o.col<int32_t>(R_CONTIG); G.o_start = o.col<int32_t>(R_START); G.o_end = o.col<int32_t>(R_END); G.o_nm = o.col<int32_t>(R_NM);
+            G.o_nu = o.col<int32_t>(R_NU); G.o_ctx = o.col<uint8_t>(R_CTX); G.o_strand = o.col<int8_t>(R_STRAND);
             const unsigned grid = (unsigned)std::min<size_t>(ge.size(), 65536);
-            hipLaunchKernelGGL(k_calls_gather, dim3(grid), dim3(CALLS_WG), 0, c->st, G);
+            hipLaunchKernelGGL(k_calls_gather, dim3(grid), dim3(CALLS_WG), 0, st, G);
             e = hipGetLastError();
-            if(e == hipSuccess) e = hipStreamSynchronize(c->st);
+            if(e == hipSuccess) e = hipStreamSynchronize(st);
         }
         if(d_ge) (void)hipFree(d_ge);
-        if(e != hipSuccess) { (void)hipFree(r->mem); delete r; return fail(MDK_ERR_HIP, "k_calls_gather", e); }
+        if(e != hipSuccess) { r->cols.release(); delete r; return fail(MDK_ERR_HIP, "k_calls_gather", e); }
     }
     c->on = false; c->used_rows = 0; c->used_tiles = 0; c->chunks.clear();
     h->no_pack = false;
@@ -339,20 +291,15 @@ extern "C" int md_calls_set_copy(const md_calls_set *c, const md_calls_cols *dst
     if(!c || !dst) return fail(MDK_ERR_ARG, "md_calls_set_copy", hipSuccess);
     HIPCHK(hipSetDevice(c->device));
     const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t n = (size_t)c->n;
-    if(!n) return 0;
-    if(dst->contig) HIPCHK(hipMemcpy(dst->contig, c->contig, n * 4, kind));
-    if(dst->start) HIPCHK(hipMemcpy(dst->start, c->start, n * 4, kind));
-    if(dst->end) HIPCHK(hipMemcpy(dst->end, c->end, n * 4, kind));
-    if(dst->nmeth) HIPCHK(hipMemcpy(dst->nmeth, c->nm, n * 4, kind));
-    if(dst->nunmeth) HIPCHK(hipMemcpy(dst->nunmeth, c->nu, n * 4, kind));
-    if(dst->context) HIPCHK(hipMemcpy(dst->context, c->ctx, n, kind));
-    if(dst->strand) HIPCHK(hipMemcpy(dst->strand, c->strand, n, kind));
+    if(!c->n) return 0;
+    void *const to[] = {dst->contig, dst->start, dst->end, dst->nmeth, dst->nunmeth, dst->context, dst->strand};        // R_CONTIG .. R_STRAND
+    for(int i = 0; i < 7; i++) if(to[i]) { const int rc = c->cols.copy_out(i, (uint64_t)c->n, to[i], kind); if(rc) return rc; }
     return 0;
 }
 
 extern "C" void md_calls_set_free(md_calls_set *c) {
     if(!c) return;
-    if(c->mem) { (void)hipSetDevice(c->device); (void)hipFree(c->mem); }
+    (void)hipSetDevice(c->device);
+    c->cols.release();
     delete c;
 }

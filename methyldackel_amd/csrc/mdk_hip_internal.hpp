@@ -210,4 +210,63 @@ MDK_HIDDEN void inflate_kernels_warm();
 MDK_HIDDEN hipStream_t mdk_piece_stream_take(int device);      // a low-priority stream for the device inflate (its own pool of hardware queues)
 MDK_HIDDEN hipStream_t mdk_stream_take(int device);       // a stream made ahead by md_dev_warm, or a new one      // mdk_inflate.hip: its code object loaded
 MDK_HIDDEN int enqueue_prep_group(md_dev *h, Slot *const *ss, int n, hipStream_t st);      // preparation kernels of up to MAXM uploaded raw slots, one launch each kernel
+// Session tables (mdk_calls.hip, mdk_reads.hip): ONE device allocation -- plain hipMalloc, not carved -- sliced into typed columns, every
+// column starting 256-byte aligned.  A run's tables are grown by doubling, never below their floor, with a copy of what they hold, and are
+// kept across runs; a result set is a table reserved once, at its exact size.
+struct ColSpec { uint32_t elem, extra; };        // bytes per entry; entries the column holds beyond the row count (the reads' name offsets: one)
+#define COLTAB_MAXK 8
+#define CALLS_ROWS_FLOOR (1u << 20)              // rows of the calls' run arena
+#define CALLS_TILES_FLOOR (1u << 14)             // entries of the calls' tile table
+#define READS_ROWS_FLOOR (1u << 18)              // rows of the reads' run arena
+#define READS_BYTES_FLOOR (1u << 22)             // name bytes of the reads' run arena
+struct ColTable {
+    const ColSpec *spec; int k; const char *what;           // `what` names the table in the allocation's error message
+    char *mem = nullptr; uint64_t cap = 0; size_t at[COLTAB_MAXK] = {};
+    ColTable(const ColSpec *s, int n, const char *w) : spec(s), k(n), what(w) {}
+    template <typename T> T *col(int i) const { return mem ? (T *)(mem + at[i]) : nullptr; }
+    // room for used + more rows.  Growing allocates max(2 * cap, used + more, floor) rows, copies the used prefix of every column on `st`,
+    // waits, frees the old block and switches; on any failure the new block is freed and the table is as it was
+    int reserve(uint64_t used, uint64_t more, uint64_t floor, hipStream_t st) {
+        if(used + more <= cap) return 0;
+        uint64_t want = cap * 2; if(want < used + more) want = used + more; if(want < floor) want = floor;
+        size_t to[COLTAB_MAXK], bytes = 0;
+        for(int i = 0; i < k; i++) { to[i] = bytes; bytes += ((size_t)(want + spec[i].extra) * spec[i].elem + 255) & ~(size_t)255; }
+        char *m = nullptr;
+        hipError_t e = hipMalloc((void **)&m, bytes);
+        if(e != hipSuccess) return fail(MDK_ERR_NOMEM, what, e);
+        if(used) {
+            for(int i = 0; i < k && e == hipSuccess; i++) e = hipMemcpyAsync(m + to[i], mem + at[i], (size_t)(used + spec[i].extra) * spec[i].elem, hipMemcpyDeviceToDevice, st);
+            if(e == hipSuccess) e = hipStreamSynchronize(st);
+            if(e != hipSuccess) { (void)hipFree(m); return fail(MDK_ERR_HIP, "copying a grown table", e); }
+        }
+        release();
+        mem = m; cap = want; memcpy(at, to, sizeof(at));
+        return 0;
+    }
+    void release() { if(mem) (void)hipFree(mem); mem = nullptr; cap = 0; }
+    int copy_out(int i, uint64_t n, void *dst, hipMemcpyKind kind) const { HIPCHK(hipMemcpy(dst, mem + at[i], (size_t)n * spec[i].elem, kind)); return 0; }
+};
+// What the calls' and the reads' state share: a stream of their own for the work on their tables, and the event that orders the slots'
+// streams after it
+struct TableLane {
+    hipStream_t st = nullptr; hipEvent_t done = nullptr;
+    int open(int device) {        // at the start of every run: made at the first, idle when this returns
+        if(!st) { st = mdk_stream_take(device); if(!st) return fail(MDK_ERR_HIP, "hipStreamCreateWithFlags", hipGetLastError()); }
+        if(!done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    void close() {                // idle before anything of the state is freed
+        if(st) (void)hipStreamSynchronize(st); if(done) (void)hipEventDestroy(done); if(st) (void)hipStreamDestroy(st); st = nullptr; done = nullptr;
+    }
+    // the slots' next work -- on their stream and, where their latest launch went elsewhere, on that one -- comes after what is queued here now
+    int fence(Slot *const *ss, int n) {
+        HIPCHK(hipEventRecord(done, st));
+        for(int i = 0; i < n; i++) {
+            HIPCHK(hipStreamWaitEvent(ss[i]->stream, done, 0));
+            if(ss[i]->run && ss[i]->run != ss[i]->stream) HIPCHK(hipStreamWaitEvent(ss[i]->run, done, 0));
+        }
+        return 0;
+    }
+};
 #endif

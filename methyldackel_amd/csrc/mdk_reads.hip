@@ -21,19 +21,24 @@
 #define READS_NAME_OFF 36u           // the name's offset from a record's block_size word; l_read_name at +12, pos at +8
 
 struct ReadsSlot { DBuf<uint32_t> loc, boff; };       // per kept read: its name's offset inside its workgroup's; per workgroup: the offset of its names in the chunk
+// columns of the rows (md_reads_cols' order; the name offsets hold one entry more: the end of the last name) and of the name bytes
+enum { C_CONTIG = 0, C_POS, C_NM, C_NU, C_OFF };
+static const ColSpec ROW_COLS[] = {{4, 0}, {4, 0}, {4, 0}, {4, 0}, {8, 1}};
+static const ColSpec BYTE_COLS[] = {{1, 0}};
+struct ReadsTables {
+    ColTable rows{ROW_COLS, 5, "hipMalloc(read rows)"}, bytes{BYTE_COLS, 1, "hipMalloc(read names)"};
+    int32_t *i32(int i) const { return rows.col<int32_t>(i); }
+    int64_t *off() const { return rows.col<int64_t>(C_OFF); }
+    uint8_t *names() const { return bytes.col<uint8_t>(0); }
+    void release() { rows.release(); bytes.release(); }
+};
 struct ReadsState {
-    hipStream_t st = nullptr; hipEvent_t done = nullptr;      // the appends run here; `done` orders the slots' next work after them
-    // the run's rows: plain hipMalloc, grown by doubling, kept across runs
-    int32_t *contig = nullptr, *pos = nullptr, *nm = nullptr, *nu = nullptr; int64_t *off = nullptr; uint64_t cap_rows = 0, used_rows = 0;
-    uint8_t *bytes = nullptr; uint64_t cap_bytes = 0, used_bytes = 0;
+    TableLane lane;                                           // the appends run here
+    ReadsTables t; uint64_t used_rows = 0, used_bytes = 0;    // the run's rows: kept across runs
     std::vector<ReadsSlot> slots;
 };
 
-struct md_reads_set {
-    int device = 0; int64_t n = 0, n_bytes = 0;
-    int32_t *contig = nullptr, *pos = nullptr, *nm = nullptr, *nu = nullptr; int64_t *off = nullptr; uint8_t *bytes = nullptr;
-    void *mem = nullptr;
-};
+struct md_reads_set { int device = 0; int64_t n = 0, n_bytes = 0; ReadsTables t; };
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -142,55 +147,17 @@ __global__ __launch_bounds__(READS_WG) void k_reads_names(const KReadsNames K) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static void reads_free_arena(ReadsState *r) {
-    for(void *p : {(void *)r->contig, (void *)r->pos, (void *)r->nm, (void *)r->nu, (void *)r->off}) if(p) (void)hipFree(p);
-    r->contig = r->pos = r->nm = r->nu = nullptr; r->off = nullptr; r->cap_rows = 0;
-    if(r->bytes) (void)hipFree(r->bytes);
-    r->bytes = nullptr; r->cap_bytes = 0;
-}
-// room for `rows` more rows (and the end offset behind them) and `bytes` more name bytes.  Growing copies what is there: every append
-// queued so far is waited for first.
+// room for `rows` more rows and `bytes` more name bytes (growing copies what is there, behind every append queued so far)
 static int reads_reserve(ReadsState *r, uint64_t rows, uint64_t bytes) {
-    if(r->used_rows + rows + 1 > r->cap_rows) {
-        const uint64_t want = std::max<uint64_t>(r->cap_rows * 2, std::max<uint64_t>(r->used_rows + rows + 1, 1u << 18));
-        HIPCHK(hipStreamSynchronize(r->st));
-        int32_t *c = nullptr, *p = nullptr, *m = nullptr, *u = nullptr; int64_t *o = nullptr;
-        hipError_t e = hipMalloc((void **)&c, want * 4);
-        if(e == hipSuccess) e = hipMalloc((void **)&p, want * 4);
-        if(e == hipSuccess) e = hipMalloc((void **)&m, want * 4);
-        if(e == hipSuccess) e = hipMalloc((void **)&u, want * 4);
-        if(e == hipSuccess) e = hipMalloc((void **)&o, want * 8);
-        if(e != hipSuccess) { for(void *q : {(void *)c, (void *)p, (void *)m, (void *)u, (void *)o}) if(q) (void)hipFree(q); return fail(MDK_ERR_NOMEM, "hipMalloc(read rows)", e); }
-        if(r->used_rows) {
-            const size_t n = (size_t)r->used_rows;
-            HIPCHK(hipMemcpyAsync(c, r->contig, n * 4, hipMemcpyDeviceToDevice, r->st)); HIPCHK(hipMemcpyAsync(p, r->pos, n * 4, hipMemcpyDeviceToDevice, r->st));
-            HIPCHK(hipMemcpyAsync(m, r->nm, n * 4, hipMemcpyDeviceToDevice, r->st)); HIPCHK(hipMemcpyAsync(u, r->nu, n * 4, hipMemcpyDeviceToDevice, r->st));
-            HIPCHK(hipMemcpyAsync(o, r->off, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st));
-            HIPCHK(hipStreamSynchronize(r->st));
-        }
-        for(void *q : {(void *)r->contig, (void *)r->pos, (void *)r->nm, (void *)r->nu, (void *)r->off}) if(q) (void)hipFree(q);
-        r->contig = c; r->pos = p; r->nm = m; r->nu = u; r->off = o; r->cap_rows = want;
-    }
-    if(r->used_bytes + bytes > r->cap_bytes) {
-        const uint64_t want = std::max<uint64_t>(r->cap_bytes * 2, std::max<uint64_t>(r->used_bytes + bytes, 1u << 22));
-        HIPCHK(hipStreamSynchronize(r->st));
-        uint8_t *b = nullptr;
-        hipError_t e = hipMalloc((void **)&b, want);
-        if(e != hipSuccess) return fail(MDK_ERR_NOMEM, "hipMalloc(read names)", e);
-        if(r->used_bytes) { e = hipMemcpy(b, r->bytes, (size_t)r->used_bytes, hipMemcpyDeviceToDevice); if(e != hipSuccess) { (void)hipFree(b); return fail(MDK_ERR_HIP, "hipMemcpy(read names)", e); } }
-        if(r->bytes) (void)hipFree(r->bytes);
-        r->bytes = b; r->cap_bytes = want;
-    }
-    return 0;
+    const int rc = r->t.rows.reserve(r->used_rows, rows, READS_ROWS_FLOOR, r->lane.st);
+    return rc ? rc : r->t.bytes.reserve(r->used_bytes, bytes, READS_BYTES_FLOOR, r->lane.st);
 }
 
 void reads_state_free(md_dev *h) {
     ReadsState *r = h->reads; if(!r) return;
-    if(r->st) (void)hipStreamSynchronize(r->st);
-    reads_free_arena(r);
+    r->lane.close();
+    r->t.release();
     for(ReadsSlot &s : r->slots) { s.loc.release(); s.boff.release(); }
-    if(r->done) (void)hipEventDestroy(r->done);
-    if(r->st) (void)hipStreamDestroy(r->st);
     delete r; h->reads = nullptr; h->reads_on = false;
 }
 
@@ -199,9 +166,7 @@ extern "C" int md_dev_reads_begin(md_dev *h) {
     HIPCHK(hipSetDevice(h->device));
     if(!h->reads) h->reads = new ReadsState();
     ReadsState *r = h->reads;
-    if(!r->st) { r->st = mdk_stream_take(h->device); if(!r->st) return fail(MDK_ERR_HIP, "hipStreamCreateWithFlags", hipGetLastError()); }
-    if(!r->done) HIPCHK(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
-    HIPCHK(hipStreamSynchronize(r->st));
+    { const int rc = r->lane.open(h->device); if(rc) return rc; }
     if(r->slots.size() < (size_t)h->n_slots) r->slots.resize((size_t)h->n_slots);
     r->used_rows = 0; r->used_bytes = 0;
     h->reads_on = true;
@@ -237,17 +202,16 @@ extern "C" int md_dev_reads_collect(md_dev *h, int slot, int64_t *n_out) {
     if(n == 0) return 0;
     { const int rc = reads_reserve(r, n, total); if(rc) return rc; }
     KReadsRows R; R.raw = s->raw_at; R.rec_at = s->rec_at; R.aidx = s->d_aidx.p; R.loc = rs.loc.p; R.boff = rs.boff.p; R.prc = s->d_prc.p; R.n = n; R.total = total; R.tid = s->tid;
-    R.row = r->used_rows; R.byte_base = r->used_bytes; R.contig = r->contig; R.pos = r->pos; R.nm = r->nm; R.nu = r->nu; R.off = r->off;
-    hipLaunchKernelGGL(k_reads_rows, dim3((n + 1 + READS_WG - 1) / READS_WG), dim3(READS_WG), 0, r->st, R);
+    R.row = r->used_rows; R.byte_base = r->used_bytes; R.contig = r->t.i32(C_CONTIG); R.pos = r->t.i32(C_POS); R.nm = r->t.i32(C_NM); R.nu = r->t.i32(C_NU); R.off = r->t.off();
+    hipLaunchKernelGGL(k_reads_rows, dim3((n + 1 + READS_WG - 1) / READS_WG), dim3(READS_WG), 0, r->lane.st, R);
     if(total) {
-        KReadsNames N; N.raw = s->raw_at; N.rec_at = s->rec_at; N.aidx = s->d_aidx.p; N.off = r->off; N.n = n; N.total = total; N.row = r->used_rows; N.byte_base = r->used_bytes; N.bytes = r->bytes;
+        KReadsNames N; N.raw = s->raw_at; N.rec_at = s->rec_at; N.aidx = s->d_aidx.p; N.off = r->t.off(); N.n = n; N.total = total; N.row = r->used_rows; N.byte_base = r->used_bytes; N.bytes = r->t.names();
         const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)total + READS_WG - 1) / READS_WG, 1u << 16);
-        hipLaunchKernelGGL(k_reads_names, dim3(grid), dim3(READS_WG), 0, r->st, N);
+        hipLaunchKernelGGL(k_reads_names, dim3(grid), dim3(READS_WG), 0, r->lane.st, N);
     }
     HIPCHK(hipGetLastError());
     // the slot's next submit comes after the appends have read its records, kept reads and counts
-    HIPCHK(hipEventRecord(r->done, r->st));
-    HIPCHK(hipStreamWaitEvent(s->stream, r->done, 0));
+    { const int rc = r->lane.fence(&s, 1); if(rc) return rc; }
     r->used_rows += n; r->used_bytes += total;
     *n_out = n;
     return 0;
@@ -263,14 +227,14 @@ extern "C" int md_dev_reads_host(md_dev *h, int32_t tid, int64_t n, const int32_
     std::vector<int32_t> ct((size_t)n, tid), nm((size_t)n, 0), nu((size_t)n, 0); std::vector<int64_t> off((size_t)n + 1);
     for(int64_t i = 0; i < n; i++) { if(counts) { nm[(size_t)i] = (int32_t)counts[i].nmeth; nu[(size_t)i] = (int32_t)counts[i].nunmeth; } off[(size_t)i] = (int64_t)(r->used_bytes + name_off[i] - name_off[0]); }
     off[(size_t)n] = (int64_t)(r->used_bytes + total);
-    const size_t row = (size_t)r->used_rows;
-    HIPCHK(hipMemcpyAsync(r->contig + row, ct.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
-    HIPCHK(hipMemcpyAsync(r->pos + row, pos, (size_t)n * 4, hipMemcpyHostToDevice, r->st));
-    HIPCHK(hipMemcpyAsync(r->nm + row, nm.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
-    HIPCHK(hipMemcpyAsync(r->nu + row, nu.data(), (size_t)n * 4, hipMemcpyHostToDevice, r->st));
-    HIPCHK(hipMemcpyAsync(r->off + row, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, r->st));
-    if(total) HIPCHK(hipMemcpyAsync(r->bytes + r->used_bytes, names + name_off[0], (size_t)total, hipMemcpyHostToDevice, r->st));
-    HIPCHK(hipStreamSynchronize(r->st));        // (the host arrays go when this returns)
+    const size_t row = (size_t)r->used_rows; hipStream_t st = r->lane.st;
+    HIPCHK(hipMemcpyAsync(r->t.i32(C_CONTIG) + row, ct.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->t.i32(C_POS) + row, pos, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->t.i32(C_NM) + row, nm.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->t.i32(C_NU) + row, nu.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->t.off() + row, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    if(total) HIPCHK(hipMemcpyAsync(r->t.names() + r->used_bytes, names + name_off[0], (size_t)total, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));        // (the host arrays go when this returns)
     r->used_rows += (uint64_t)n; r->used_bytes += total;
     return 0;
 }
@@ -281,23 +245,21 @@ extern "C" int md_dev_reads_finish(md_dev *h, md_reads_set **out) {
     HIPCHK(hipSetDevice(h->device));
     ReadsState *r = h->reads;
     h->reads_on = false;
-    HIPCHK(hipStreamSynchronize(r->st));
+    hipStream_t st = r->lane.st;
+    HIPCHK(hipStreamSynchronize(st));
     md_reads_set *q = new md_reads_set(); q->device = h->device; q->n = (int64_t)r->used_rows; q->n_bytes = (int64_t)r->used_bytes;
-    const size_t n = (size_t)q->n, a4 = (n * 4 + 255) & ~(size_t)255, a8 = ((n + 1) * 8 + 255) & ~(size_t)255, ab = ((size_t)q->n_bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&q->mem, 4 * a4 + a8 + ab + 256);
-    if(e != hipSuccess) { delete q; return fail(MDK_ERR_NOMEM, "hipMalloc(reads)", e); }
-    char *m = (char *)q->mem;
-    q->contig = (int32_t *)m; q->pos = (int32_t *)(m + a4); q->nm = (int32_t *)(m + 2 * a4); q->nu = (int32_t *)(m + 3 * a4); q->off = (int64_t *)(m + 4 * a4); q->bytes = (uint8_t *)(m + 4 * a4 + a8);
+    const uint64_t n = r->used_rows;
+    // at their exact size (an empty set still holds its one offset, 0); the run's columns copied one by one
+    int rc = q->t.rows.reserve(0, std::max<uint64_t>(n, 1), 0, st);
+    if(!rc) rc = q->t.bytes.reserve(0, r->used_bytes, 0, st);
+    if(rc) { q->t.release(); delete q; return rc; }
+    hipError_t e = hipSuccess;
     if(n) {
-        e = hipMemcpyAsync(q->contig, r->contig, n * 4, hipMemcpyDeviceToDevice, r->st);
-        if(e == hipSuccess) e = hipMemcpyAsync(q->pos, r->pos, n * 4, hipMemcpyDeviceToDevice, r->st);
-        if(e == hipSuccess) e = hipMemcpyAsync(q->nm, r->nm, n * 4, hipMemcpyDeviceToDevice, r->st);
-        if(e == hipSuccess) e = hipMemcpyAsync(q->nu, r->nu, n * 4, hipMemcpyDeviceToDevice, r->st);
-        if(e == hipSuccess) e = hipMemcpyAsync(q->off, r->off, (n + 1) * 8, hipMemcpyDeviceToDevice, r->st);
-        if(e == hipSuccess && q->n_bytes) e = hipMemcpyAsync(q->bytes, r->bytes, (size_t)q->n_bytes, hipMemcpyDeviceToDevice, r->st);
-    } else e = hipMemsetAsync(q->off, 0, 8, r->st);
-    if(e == hipSuccess) e = hipStreamSynchronize(r->st);
-    if(e != hipSuccess) { (void)hipFree(q->mem); delete q; return fail(MDK_ERR_HIP, "md_dev_reads_finish: copies", e); }
+        for(int i = 0; i < 5 && e == hipSuccess; i++) e = hipMemcpyAsync(q->t.rows.col<char>(i), r->t.rows.col<char>(i), (size_t)(n + ROW_COLS[i].extra) * ROW_COLS[i].elem, hipMemcpyDeviceToDevice, st);
+        if(e == hipSuccess && q->n_bytes) e = hipMemcpyAsync(q->t.names(), r->t.names(), (size_t)q->n_bytes, hipMemcpyDeviceToDevice, st);
+    } else e = hipMemsetAsync(q->t.off(), 0, 8, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) { q->t.release(); delete q; return fail(MDK_ERR_HIP, "md_dev_reads_finish: copies", e); }
     r->used_rows = 0; r->used_bytes = 0;
     *out = q;
     return 0;
@@ -310,19 +272,17 @@ extern "C" int md_reads_set_copy(const md_reads_set *r, const md_reads_cols *dst
     if(!r || !dst) return fail(MDK_ERR_ARG, "md_reads_set_copy", hipSuccess);
     HIPCHK(hipSetDevice(r->device));
     const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    const size_t n = (size_t)r->n;
-    if(dst->name_off) HIPCHK(hipMemcpy(dst->name_off, r->off, (n + 1) * 8, kind));
-    if(dst->name_bytes && r->n_bytes) HIPCHK(hipMemcpy(dst->name_bytes, r->bytes, (size_t)r->n_bytes, kind));
-    if(!n) return 0;
-    if(dst->contig) HIPCHK(hipMemcpy(dst->contig, r->contig, n * 4, kind));
-    if(dst->pos) HIPCHK(hipMemcpy(dst->pos, r->pos, n * 4, kind));
-    if(dst->nmeth) HIPCHK(hipMemcpy(dst->nmeth, r->nm, n * 4, kind));
-    if(dst->nunmeth) HIPCHK(hipMemcpy(dst->nunmeth, r->nu, n * 4, kind));
+    const uint64_t n = (uint64_t)r->n;
+    void *const to[] = {dst->contig, dst->pos, dst->nmeth, dst->nunmeth, dst->name_off};        // C_CONTIG .. C_OFF
+    for(int i = 0; i < 5; i++)         // (an empty set still copies its one name offset, 0)
+        if(to[i] && n + ROW_COLS[i].extra) { const int rc = r->t.rows.copy_out(i, n + ROW_COLS[i].extra, to[i], kind); if(rc) return rc; }
+    if(dst->name_bytes && r->n_bytes) return r->t.bytes.copy_out(0, (uint64_t)r->n_bytes, dst->name_bytes, kind);
     return 0;
 }
 
 extern "C" void md_reads_set_free(md_reads_set *r) {
     if(!r) return;
-    if(r->mem) { (void)hipSetDevice(r->device); (void)hipFree(r->mem); }
+    (void)hipSetDevice(r->device);
+    r->t.release();
     delete r;
 }

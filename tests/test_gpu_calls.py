@@ -180,3 +180,31 @@ def test_no_leak_over_ten_calls(session, sdata):
     cur1 = int(open("/proc/self/statm").read().split()[1]) * os.sysconf("SC_PAGE_SIZE")
     assert free0 - free1 <= 64 << 20, (free0, free1)
     assert cur1 - cur0 <= 64 << 20, (cur0, cur1, rss0)
+
+
+def test_tables_grow_with_rows_in_them(session, tmp_path):
+    """a sample past the floors of both run tables (CALLS_ROWS_FLOOR = 1 << 20 rows, CALLS_TILES_FLOOR = 1 << 14 tiles in
+    mdk_hip_internal.hpp): nine 1 Mb chunks in two groups (a group holds at most eight), so the later group makes the row arena and the tile
+    table grow with the earlier group's rows and tiles in them.  Twice on the module's session -- the second run starts from the grown
+    tables -- with equal columns, and rows equal to the command's"""
+    import torch
+    synth(tmp_path / "g", "-L", "9000000", "-c", "4", "-s", "7")
+    length = sum(len(l.strip()) for l in open(tmp_path / "g.fa") if not l.startswith(">"))
+    args = [tmp_path / "g.fa", tmp_path / "g.bam", "-@", "4", "--CHG", "--CHH"]
+    env = {"MDK_TILE": "512"}
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        c, again = session.extract(args), session.extract(args)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    print("rows", len(c), "tiles of 512 at least", length // 512)
+    assert len(c) > 1 << 20
+    assert length // 512 > 1 << 14
+    for name in ("contig", "start", "end", "nmeth", "nunmeth", "context", "strand"):
+        assert torch.equal(getattr(c, name), getattr(again, name)), name
+    assert same(c, cli_rows(tmp_path, args, "cli", env=env)) == len(c)

@@ -208,3 +208,20 @@ def test_no_leak_over_ten_calls(session, small_synth, tmp_path):
     cur1 = int(open("/proc/self/statm").read().split()[1]) * os.sysconf("SC_PAGE_SIZE")
     assert free0 - free1 <= 64 << 20, (free0, free1)
     assert cur1 - cur0 <= 64 << 20, (cur0, cur1)
+
+
+def test_tables_grow_with_rows_in_them(session, tmp_path):
+    """a sample past the floors of both run tables (READS_ROWS_FLOOR = 1 << 18 rows, READS_BYTES_FLOOR = 1 << 22 name bytes in
+    mdk_hip_internal.hpp), in three chunks none of which passes a floor alone: the tables are appended at exact size, so the rows grow at
+    the second and third chunk and the name bytes at the third, each time with the earlier chunks' rows in them.  Twice on the module's
+    session -- the second run starts from the grown tables -- with equal columns, and rows rendered as the command prints them"""
+    import torch
+    synth(tmp_path / "g", "-L", "3000000", "-c", "30", "-s", "7")
+    args = [tmp_path / "g.fa", tmp_path / "g.bam"]
+    r, again = session.perread(args), session.perread(args)
+    print("rows", len(r), "name bytes", r.name_bytes.numel())
+    assert len(r) > 1 << 18
+    assert r.name_bytes.numel() > 1 << 22
+    for name in ("contig", "pos", "nmeth", "nunmeth", "name_offsets", "name_bytes"):
+        assert torch.equal(getattr(r, name), getattr(again, name)), name
+    assert render(r) == cli_text(tmp_path, args)
