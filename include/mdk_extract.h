@@ -112,6 +112,10 @@ void mdk_cli_quiesce(void);
 int  mdk_plan_open_mbias(int argc, char *argv[], mdk_plan **out);
 int  mdk_plan_mbias_outputs(const mdk_plan *p, const char **opref, int *svg, int *txt, int *which);
 int  mdk_mbias_report(const md_mbias *hist, const char *opref, int svg, int txt, int which);
+/* the report's inclusion bounds on their own (getThresholds, svg.c:239-294): bounds[4 * strand + {0,1,2,3}] = read 1 left, right, read 2 left,
+ * right and has[strand] = 1 for every strand (0..3 = OT, OB, CTOT, CTOB) that has a call -- the numbers mdk_mbias_report prints behind
+ * "Suggested inclusion options:" when it draws the plots.  Returns 0, -1 for a bad argument. */
+int  mdk_mbias_suggest(const md_mbias *hist, int bounds[16], int has[4]);
 
 /* ---- `perRead` (perRead.c; main.c:20,55-56 dispatches to perRead_main) ----
  * perRead_main: drop-in for the reference symbol (argv[0] = "perRead").  mdk_plan_open_perread: chunks without
@@ -182,6 +186,29 @@ int  mdk_reads_n_contigs(const mdk_reads *r);
 const char *mdk_reads_contig_name(const mdk_reads *r, int i);
 int  mdk_reads_copy(const mdk_reads *r, int column, void *dst, int to_host);
 void mdk_reads_free(mdk_reads *r);
+
+/* ---- the same session's mbias: the methylation-bias table as device-resident columns ----
+ * mdk_session_mbias takes the argv of mbias_main (argv[0] = "mbias"), parses it with the same code and returns the same codes for the same
+ * errors -- a command line without --noSVG still needs its output prefix (rc -1 without it).  The prefix is ignored: no SVG is written,
+ * nothing is printed to stdout, --txt changes nothing.  What comes back (include/mdk_hip.h "the methylation-bias table on the device"):
+ *   the table's rows in the order the command prints them -- MDK_BIAS_STRAND (int8, 0..3 = OT, OB, CTOT, CTOB), MDK_BIAS_READ (int8, 1 or 2),
+ *   MDK_BIAS_POSITION (int32, 1-based), MDK_BIAS_NMETH, MDK_BIAS_NUNMETH (int64) --, MDK_BIAS_COUNTS, the dense histogram as int64
+ *   [mdk_bias_len][4][2][2] (position, strand, read, methylated/unmethylated), and the inclusion bounds the command suggests when it draws
+ *   its plots, always computed here: mdk_bias_suggested(b, strand, bounds) returns 1 and the strand's four numbers when the strand has a call.
+ * mdk_bias_resubmitted: chunks of the run whose group launch left them out (a read longer than the histogram, more segments than reserved)
+ * and that were counted through the single-chunk path instead.  -h / --version return 0 and an empty mdk_bias.  A chunk of a contig the FASTA
+ * lacks ends the run with -4, a read of unknown strand aborts, both as in mbias_main.  The run uses the slots and streams of an extract run
+ * (groups of up to eight chunks per launch, md_dev_mbias_group), so the three commands alternate on one handle.
+ * Ownership and lifetimes are those of mdk_calls; mdk_bias_copy is synchronous (mdk_bias_count entries, 16 * mdk_bias_len for MDK_BIAS_COUNTS). */
+typedef struct mdk_bias mdk_bias;
+enum { MDK_BIAS_STRAND = 0, MDK_BIAS_READ, MDK_BIAS_POSITION, MDK_BIAS_NMETH, MDK_BIAS_NUNMETH, MDK_BIAS_COUNTS };   /* int8 x2, int32, int64 x3 */
+int  mdk_session_mbias(mdk_session *s, int argc, char *argv[], mdk_bias **out);
+int64_t mdk_bias_count(const mdk_bias *b);
+int64_t mdk_bias_len(const mdk_bias *b);
+int64_t mdk_bias_resubmitted(const mdk_bias *b);
+int  mdk_bias_suggested(const mdk_bias *b, int strand, int bounds[4]);
+int  mdk_bias_copy(const mdk_bias *b, int column, void *dst, int to_host);
+void mdk_bias_free(mdk_bias *b);
 
 /* ---- `mergeContext` (mergeContext.c; main.c:19,53-54): text-to-text host tool, no device work ---- */
 int  mergeContext_main(int argc, char *argv[]);

@@ -276,6 +276,39 @@ int  md_dev_mbias_submit_raw(md_dev *h, int slot, const md_raw_batch *b);
 int  md_dev_mbias_read(md_dev *h, md_mbias *out);
 int  md_dev_mbias_reset(md_dev *h);
 int  md_dev_slot_sync(md_dev *h, int slot);
+/* Group launches (k_mbias_multi): up to md_dev_group_max() slots, each freshly uploaded with md_dev_upload_raw / _inplace (md_dev_set_prep with
+ * no_pairing first, the contigs' references resident), get their preparation and their histogram with one launch per kernel on the first
+ * slot's stream (with CHG or CHH on, the histogram gets one launch per chunk instead, queued by the same call: eight dense chunks in one launch
+ * were measured slower).  The call queues and returns: the host does not wait between preparation and histogram kernel -- how many histogram rows a
+ * chunk keeps in LDS, and whether it may count at all, the kernel reads from the chunk's status block on the device.  A chunk adds its counts
+ * exactly once: one whose preparation did not end cleanly, or whose longest admitted read has more positions than the histogram has rows, adds
+ * nothing and says so in its status.  md_dev_mbias_collect(the same slots) waits for the launch; rc[i] is 0 or what the chunk's preparation
+ * reported (MDK_ERR_PREP_HOST: prepare it on the host and give it to md_dev_mbias_submit; MDK_ERR_STRAND0; MDK_ERR_ARG for a malformed record),
+ * and the chunks the device skipped for want of room go through the single-chunk path there and then (their preparation again, the histogram
+ * grown with the device drained, k_mbias), so the records must stay valid until it returns.  md_dev_mbias_redone: how many chunks that were,
+ * since the last reset / md_dev_bias_finish.  md_dev_mbias_group and md_dev_mbias_collect may be called by two threads (one each). */
+int  md_dev_mbias_group(md_dev *h, const int *slots, int n);
+int  md_dev_mbias_collect(md_dev *h, const int *slots, int n, int *rc);
+int  md_dev_mbias_redone(const md_dev *h);
+
+/* The methylation-bias table on the device (csrc/mdk_bias.hip): what a resident session returns for an `mbias` run.  md_dev_bias_finish waits
+ * for every histogram kernel (MDK_ERR_STRAND0 as md_dev_mbias_read) and turns the histogram into a md_bias_set (k_bias_rows):
+ *   - the rows of the command's table in the order it prints them (strand OT, OB, CTOT, CTOB; ascending position; read 1 then read 2; only
+ *     where nmeth || nunmeth): MD_BIAS_STRAND int8 0..3, MD_BIAS_READ int8 1|2, MD_BIAS_POS int32 1-based, MD_BIAS_NMETH / MD_BIAS_NUNMETH int64;
+ *   - MD_BIAS_COUNTS: the dense histogram, int64 [len][4][2][2] (position, strand, read, methylated/unmethylated), len = the longest admitted read;
+ *   - the histogram on the host (md_bias_set_hist: memory of the set), from which the caller computes the inclusion bounds.
+ * The set owns its device memory at its exact size, independent of the handle (it may outlive it), until md_bias_set_free.  The handle's
+ * histogram stays as it is (md_dev_reset / md_dev_mbias_reset drop it). */
+typedef struct md_bias_set md_bias_set;
+enum { MD_BIAS_STRAND = 0, MD_BIAS_READ, MD_BIAS_POS, MD_BIAS_NMETH, MD_BIAS_NUNMETH, MD_BIAS_COUNTS };
+int  md_dev_bias_finish(md_dev *h, md_bias_set **out);
+int64_t md_bias_set_count(const md_bias_set *b);          /* rows */
+int  md_bias_set_len(const md_bias_set *b);               /* positions of the dense histogram */
+int  md_bias_set_redone(const md_bias_set *b);            /* chunks of the run that went through the single-chunk path after a group launch */
+int  md_bias_set_hist(const md_bias_set *b, md_mbias *out);
+/* synchronous copy of one column (count entries; MD_BIAS_COUNTS: 16 * len) into DEVICE memory of the set's device (to_host = 0) or host memory */
+int  md_bias_set_copy(const md_bias_set *b, int column, void *dst, int to_host);
+void md_bias_set_free(md_bias_set *b);
 
 /* perRead (perRead.c): per-read CpG methylation.  One md_pr_read per alignment the command keeps (start inside the chunk,
  * -F/-R/-q passed), in file order; `cigar` holds the BAM CIGAR words of all reads back to back (cig_off/n_cigar index it);

@@ -164,6 +164,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_bench_open", "md_bench_run", "md_bench_verify", "md_bench_region_bytes", "md_bench_close", "md_dev_debug_effective", "md_host_alloc", "md_host_free", "md_host_set_pinned", "md_host_profile", "md_dev_profile_text", "md_host_register", "md_host_register_all",
                "md_dev_set_prep", "md_dev_set_mappability", "md_dev_upload_raw", "md_dev_upload_raw_inplace", "md_dev_upload_wait", "md_dev_upload_done", "md_dev_submit_raw", "md_dev_debug_segments", "md_dev_bench_prep", "md_dev_bench_prep_rotate", "md_bench_set_prep",
                "md_dev_mbias_submit", "md_dev_mbias_submit_raw", "md_dev_mbias_read", "md_dev_mbias_reset", "md_dev_slot_sync",
+               "md_dev_mbias_group", "md_dev_mbias_collect", "md_dev_mbias_redone", "md_dev_bias_finish", "md_bias_set_count", "md_bias_set_len", "md_bias_set_redone", "md_bias_set_hist", "md_bias_set_copy", "md_bias_set_free",
                "md_dev_perread_submit", "md_dev_perread_download", "md_dev_perread_submit_raw", "md_dev_perread_download_raw", "md_dev_read_raw",
                "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
@@ -175,7 +176,8 @@ EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_
                    "mbias_main", "mdk_cli_quiesce", "mdk_plan_open_mbias", "mdk_plan_mbias_outputs", "mdk_mbias_report",
                    "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node",
                    "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free",
-                   "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free"]
+                   "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free",
+                   "mdk_mbias_suggest", "mdk_session_mbias", "mdk_bias_count", "mdk_bias_len", "mdk_bias_resubmitted", "mdk_bias_suggested", "mdk_bias_copy", "mdk_bias_free"]
 
 _hip = None
 _ext = None
@@ -240,6 +242,9 @@ def lib_hip():
         L.md_dev_mbias_read.argtypes = [C.c_void_p, C.POINTER(md_mbias)]
         L.md_dev_mbias_reset.argtypes = [C.c_void_p]
         L.md_dev_slot_sync.argtypes = [C.c_void_p, C.c_int]
+        L.md_dev_mbias_group.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
+        L.md_dev_mbias_collect.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.md_dev_mbias_redone.argtypes = [C.c_void_p]
         L.md_dev_perread_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(md_pr_batch)]
         L.md_dev_perread_download.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(md_pr_count)), C.POINTER(C.c_int64)]
         L.md_dev_perread_submit_raw.argtypes = [C.c_void_p, C.c_int, C.POINTER(md_raw_batch)]
@@ -284,6 +289,7 @@ def lib_extract():
         L.mdk_plan_open_mbias.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
         L.mdk_plan_mbias_outputs.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mdk_mbias_report.argtypes = [C.POINTER(md_mbias), C.c_char_p, C.c_int, C.c_int, C.c_int]
+        L.mdk_mbias_suggest.argtypes = [C.POINTER(md_mbias), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.perRead_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         L.mergeContext_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         L.mdk_plan_open_perread.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
@@ -393,6 +399,16 @@ class Device:
 
     def mbias_submit_raw(self, slot: int, raw: "md_raw_batch"):
         self._chk(self.L.md_dev_mbias_submit_raw(self.h, slot, C.byref(raw)), "md_dev_mbias_submit_raw")
+
+    def mbias_group(self, slots):
+        """md_dev_mbias_group + md_dev_mbias_collect over freshly uploaded raw slots (upload_raw): their preparation and histogram with one launch
+        per kernel, nothing waited for in between; returns the per-chunk codes and how many chunks the run has sent through the single-chunk path"""
+        n = len(slots)
+        arr = (C.c_int * n)(*slots)
+        rcs = (C.c_int * n)()
+        self._chk(self.L.md_dev_mbias_group(self.h, arr, n), "md_dev_mbias_group")
+        self._chk(self.L.md_dev_mbias_collect(self.h, arr, n, rcs), "md_dev_mbias_collect")
+        return list(rcs), int(self.L.md_dev_mbias_redone(self.h))
 
     def slot_sync(self, slot: int):
         self._chk(self.L.md_dev_slot_sync(self.h, slot), "md_dev_slot_sync")
@@ -563,6 +579,17 @@ def mbias_report(hist, opref, svg: bool, txt: bool, which: int) -> int:
     return lib_extract().mdk_mbias_report(C.byref(m), os.fsencode(str(opref)) if opref is not None else None, int(svg), int(txt), which)
 
 
+def mbias_suggest(hist):
+    """mdk_mbias_suggest over rows [q][16] (any integer array-like): {"OT": (a, b, c, d), ...} for the strands that have calls"""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(hist, dtype=np.uint32).reshape(-1))
+    m = md_mbias(len(a) // 16, a.ctypes.data_as(C.POINTER(C.c_uint32)))
+    bounds, has = (C.c_int * 16)(), (C.c_int * 4)()
+    if lib_extract().mdk_mbias_suggest(C.byref(m), bounds, has):
+        raise MdkError("mdk_mbias_suggest failed")
+    return {STRANDS[k]: tuple(bounds[4 * k:4 * k + 4]) for k in range(4) if has[k]}
+
+
 def sites_to_rows(s: md_sites):
     """md_sites -> list of (pos, type, isG, nmeth, nunmeth, noff, nvar) tuples (for tests)."""
     rows = []
@@ -631,6 +658,8 @@ def run_ranks(args, n, cwd=None, env=None, command="extract", devices=None, time
 RC_UNSUPPORTED = -23
 CALL_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("context", "uint8"), ("strand", "int8"))
 READ_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("name_offsets", "int64"), ("name_bytes", "uint8"))
+BIAS_COLUMNS = (("strand", "int8"), ("read", "int8"), ("position", "int32"), ("nmeth", "int64"), ("nunmeth", "int64"), ("counts", "int64"))
+STRANDS = ("OT", "OB", "CTOT", "CTOB")
 
 
 def _session_lib():
@@ -648,6 +677,13 @@ def _session_lib():
             getattr(L, f"mdk_{kind}_contig_name").restype = C.c_char_p
             getattr(L, f"mdk_{kind}_copy").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
             getattr(L, f"mdk_{kind}_free").argtypes = [C.c_void_p]
+        L.mdk_session_mbias.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+        for f in ("count", "len", "resubmitted"):
+            getattr(L, f"mdk_bias_{f}").argtypes = [C.c_void_p]
+            getattr(L, f"mdk_bias_{f}").restype = C.c_int64
+        L.mdk_bias_suggested.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.mdk_bias_copy.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.mdk_bias_free.argtypes = [C.c_void_p]
         L._session_types = True
     return L
 
@@ -662,7 +698,20 @@ class _Columns:
             setattr(self, name, columns[name])
 
     def __len__(self):
-        return int(self.contig.shape[0])
+        return int(getattr(self, self.COLUMNS[0][0]).shape[0])
+
+    # what Session._run asks of a result kind: the entries of the columns that do not hold one per row, and the object from the filled columns
+    KIND = ""
+    ALWAYS = ()          # columns that hold entries even when there is no row
+
+    @classmethod
+    def _sizes(cls, L, out, n):
+        return {}
+
+    @classmethod
+    def _build(cls, L, out, cols):
+        k = cls.KIND
+        return cls([getattr(L, f"mdk_{k}_contig_name")(out, i).decode() for i in range(getattr(L, f"mdk_{k}_n_contigs")(out))], cols)
 
 
 class Calls(_Columns):
@@ -670,6 +719,7 @@ class Calls(_Columns):
     ascending `start`): ``contig`` (int32, index into ``contigs``, BAM header order), ``start``/``end`` (int32, bedGraph columns 2-3),
     ``nmeth``/``nunmeth`` (int32), ``context`` (uint8: 0 CpG, 1 CHG, 2 CHH) and ``strand`` (int8: +1 C, -1 G, 0 a --mergeContext row)."""
     COLUMNS = CALL_COLUMNS
+    KIND = "calls"
 
     def rows(self, context=None):
         """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
@@ -683,6 +733,11 @@ class Reads(_Columns):
     prints 100*nmeth/(nmeth+nunmeth) and the sum), ``name_offsets`` (int64, len + 1 entries, the first 0) and ``name_bytes`` (uint8, the read
     names packed without separators: name i is name_bytes[name_offsets[i]:name_offsets[i + 1]])."""
     COLUMNS = READ_COLUMNS
+    KIND = "reads"
+
+    @classmethod
+    def _sizes(cls, L, out, n):
+        return {"name_offsets": n + 1, "name_bytes": int(L.mdk_reads_name_bytes(out))}
 
     def names(self):
         """the read names on the host, as str"""
@@ -693,6 +748,46 @@ class Reads(_Columns):
         """(name, chrom, pos, nmeth, nunmeth) tuples on the host"""
         cols = [getattr(self, n).cpu().tolist() for n in ("contig", "pos", "nmeth", "nunmeth")]
         return [(q, self.contigs[c], p, m, u) for q, c, p, m, u in zip(self.names(), *cols)]
+
+
+class Bias(_Columns):
+    """What `mbias` would print, as columns: one row per line of its table, in the command's order (strand OT, OB, CTOT, CTOB; ascending
+    position; read 1 then read 2; only positions with a call) -- ``strand`` (int8, index into STRANDS), ``read`` (int8, 1 or 2), ``position``
+    (int32, 1-based), ``nmeth``/``nunmeth`` (int64) -- and ``counts``, the dense histogram, int64 [len, 4, 2, 2] (position, strand, read,
+    methylated/unmethylated; len = the longest admitted read).  On the host: ``suggested``, the inclusion bounds the command prints behind
+    "Suggested inclusion options:" when it draws its plots ({"OT": (a, b, c, d), ...}, the strands that have calls, in STRANDS order), and
+    ``resubmitted``, the chunks whose group launch left them out and that were counted by a launch of their own.  No ``contigs``."""
+    COLUMNS = BIAS_COLUMNS
+    KIND = "bias"
+    ALWAYS = ("counts",)
+
+    @classmethod
+    def _sizes(cls, L, out, n):
+        return {"counts": 16 * int(L.mdk_bias_len(out))}
+
+    @classmethod
+    def _build(cls, L, out, cols):
+        suggested, b4 = {}, (C.c_int * 4)()
+        for k, name in enumerate(STRANDS):
+            if L.mdk_bias_suggested(out, k, b4) == 1:
+                suggested[name] = tuple(b4)
+        cols["counts"] = cols["counts"].reshape(-1, 4, 2, 2)
+        return cls(cols, suggested, int(L.mdk_bias_resubmitted(out)))
+
+    def __init__(self, columns, suggested, resubmitted=0):
+        for name, _ in self.COLUMNS:
+            setattr(self, name, columns[name])
+        self.suggested = suggested
+        self.resubmitted = resubmitted
+
+    def options(self):
+        """the suggestion as argv tokens, ["--OT", "a,b,c,d", "--OB", ...]: ready to append to an extract command line"""
+        return [t for k, v in self.suggested.items() for t in ("--" + k, ",".join(str(x) for x in v))]
+
+    def rows(self):
+        """(strand name, read, position, nmeth, nunmeth) tuples on the host: the lines of the --txt table"""
+        cols = [getattr(self, n).cpu().tolist() for n in ("strand", "read", "position", "nmeth", "nunmeth")]
+        return [(STRANDS[s], r, p, m, u) for s, r, p, m, u in zip(*cols)]
 
 
 class Session:
@@ -712,13 +807,13 @@ class Session:
             raise _rc_error("mdk_session_open", rc)
         self._h = h
 
-    def _run(self, command, kind, result, args, device_tensors):
+    def _run(self, command, result, args, device_tensors):
         """one run of `command` on the handle: its mdk_<kind> object copied, column by column, into tensors -- device to device into
         tensors torch allocated on the session's device, or into CPU tensors -- and freed"""
         import torch
         if self._h is None:
             raise MdkError("the session is closed")
-        L = self._L
+        L, kind = self._L, result.KIND
         argv = [command] + [str(a) for a in args]
         arr = (C.c_char_p * (len(argv) + 1))(*[os.fsencode(a) for a in argv], None)
         out = C.c_void_p()
@@ -727,28 +822,34 @@ class Session:
             raise _rc_error(command, rc)
         try:
             n = int(getattr(L, f"mdk_{kind}_count")(out))
-            size = {"name_offsets": n + 1, "name_bytes": int(L.mdk_reads_name_bytes(out)) if kind == "reads" else 0}      # every other column: n
-            contigs = [getattr(L, f"mdk_{kind}_contig_name")(out, i).decode() for i in range(getattr(L, f"mdk_{kind}_n_contigs")(out))]
+            size = result._sizes(L, out, n)                     # every other column: n
             dev = torch.device("cuda", self.device) if device_tensors else torch.device("cpu")
             cols = {}
             for k, (name, dt) in enumerate(result.COLUMNS):
-                t = (torch.empty if n else torch.zeros)(size.get(name, n), dtype=getattr(torch, dt), device=dev)
-                if n and t.numel():
+                m = size.get(name, n)
+                t = (torch.empty if n else torch.zeros)(m, dtype=getattr(torch, dt), device=dev)
+                if m and (n or name in result.ALWAYS):
                     rc = getattr(L, f"mdk_{kind}_copy")(out, k, C.c_void_p(t.data_ptr()), 0 if device_tensors else 1)
                     if rc:
                         raise _rc_error(f"copying the {name} column", rc)
                 cols[name] = t
+            return result._build(L, out, cols)
         finally:
             getattr(L, f"mdk_{kind}_free")(out)
-        return result(contigs, cols)
 
     def extract(self, args, device_tensors: bool = True) -> Calls:
-        return self._run("extract", "calls", Calls, args, device_tensors)
+        return self._run("extract", Calls, args, device_tensors)
 
     def perread(self, args, device_tensors: bool = True) -> Reads:
         """The `perRead` command line (without the command name) on the same handle: the rows it would print, as Reads.  -o is ignored;
         any non-zero return code raises MdkError with ``.rc``.  Extract and perRead runs may alternate on one session."""
-        return self._run("perRead", "reads", Reads, args, device_tensors)
+        return self._run("perRead", Reads, args, device_tensors)
+
+    def mbias(self, args, device_tensors: bool = True) -> Bias:
+        """The `mbias` command line (without the command name) on the same handle: its table, the dense histogram and the suggested inclusion
+        bounds, as Bias.  Parsed as the command parses it (without --noSVG the output prefix is still required), but the prefix is ignored:
+        no SVG is written and nothing is printed.  ``s.extract(args + b.options())`` is the run the suggestion is for."""
+        return self._run("mbias", Bias, args, device_tensors)
 
     def close(self):
         if self._h is not None:

@@ -134,3 +134,20 @@ int mbias_main(int argc, char *argv[]) {
     return ret;
 }
 
+
+/* ---- the session's mbias (include/mdk_extract.h): the run is mdk_extract.c's pipeline with the histogram sink ---- */
+int mdk_session_mbias(mdk_session *s, int argc, char *argv[], mdk_bias **out) { return session_run(s, argc, argv, (void **)out, sizeof(mdk_bias), session_mbias_run); }
+int64_t mdk_bias_count(const mdk_bias *b) { return b ? b->r.n : -1; }
+int64_t mdk_bias_len(const mdk_bias *b) { return b ? b->len : -1; }
+int64_t mdk_bias_resubmitted(const mdk_bias *b) { return b ? b->redone : -1; }
+int mdk_bias_suggested(const mdk_bias *b, int strand, int bounds[4]) {
+    if(!b || !bounds || strand < 0 || strand > 3) return MDK_ERR_ARG;
+    memcpy(bounds, b->bounds + 4 * strand, 4 * sizeof(int));
+    return b->has[strand];
+}
+int mdk_bias_copy(const mdk_bias *b, int column, void *dst, int to_host) {
+    if(!b || !dst || column < 0 || column > MDK_BIAS_COUNTS) return MDK_ERR_ARG;
+    if(!b->r.set) return 0;
+    return md_bias_set_copy(b->r.set, column, dst, to_host);
+}
+void mdk_bias_free(mdk_bias *b) { if(b) { md_bias_set_free(b->r.set); session_result_free(&b->r); } }

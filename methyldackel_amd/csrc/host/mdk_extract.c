@@ -84,10 +84,12 @@ MDK_LOCAL void *devopen_main(void *arg) { devopen_t *d = arg; d->rc = md_dev_ope
 static int g_ngroups = 3;            /* groups in flight (MDK_GROUPS_IN_FLIGHT=n, 2..6) */
 #define MDK_NGROUPS g_ngroups
 enum { G_FREE = 0, G_FILL, G_LAUNCHED };
-typedef struct { mdk_chunk ch[MDK_GROUP]; int slot[MDK_GROUP]; int n, launched[MDK_GROUP], inplace[MDK_GROUP], state, held, n_held, rel_slot[MDK_GROUP]; mdk_chunk rel_ch[MDK_GROUP]; } cgroup;      /* held: the host memory behind its records has not been given back yet; inplace: the device reads the chunk's records where the piece they were inflated in holds them (md_dev_upload_raw_inplace): that piece goes back when the chunk's results are in */
+enum { SINK_TEXT = 0, SINK_CALLS, SINK_BIAS };      /* where collected groups go: the text emitter (extract_main); the device calls of a session (md_dev_calls_group); the mbias
+                                                     * histogram of a session -- nothing comes back per chunk, the collector reads the group's status blocks (md_dev_mbias_collect) */
+typedef struct { mdk_chunk ch[MDK_GROUP]; int slot[MDK_GROUP]; int n, launched[MDK_GROUP], inplace[MDK_GROUP], single[MDK_GROUP], state, held, n_held, rel_slot[MDK_GROUP]; mdk_chunk rel_ch[MDK_GROUP]; } cgroup;      /* held: the host memory behind its records has not been given back yet; inplace: the device reads the chunk's records where the piece they were inflated in holds them (md_dev_upload_raw_inplace): that piece goes back when the chunk's results are in */
 typedef struct {
     mdk_plan *p; md_dev *dev; emitter *em; cgroup G[MDK_NGROUPS_MAX];
-    int calls;                           /* the sink of collected groups: 0 the text emitter (extract_main), 1 the device calls of a session (md_dev_calls_group) */
+    int sink;                            /* SINK_* */
     pthread_mutex_t mu; pthread_cond_t cv;
     int ret, up_done;                    /* (mu) first error; the uploader has launched its last group */
     uint64_t n_up, n_col;                /* (mu) groups launched / collected: group k lives in G[k % MDK_NGROUPS] */
@@ -158,16 +160,26 @@ static void *collector_main(void *arg) {
     xpipe *X = arg; mdk_plan *p = X->p; md_dev *dev = X->dev; int i;
     for(;;) {
         cgroup *g; int ls[MDK_GROUP], li[MDK_GROUP], nl = 0, rcs[MDK_GROUP], rc = 0, bad = 0; md_sites st[MDK_GROUP], sites[MDK_GROUP]; double ta;
+        memset(st, 0, sizeof(st));
         pthread_mutex_lock(&X->mu);
         while(X->n_col == X->n_up && !X->up_done && !X->ret) pthread_cond_wait(&X->cv, &X->mu);
         if(X->ret || X->n_col == X->n_up) { pthread_mutex_unlock(&X->mu); break; }
         g = &X->G[X->n_col % MDK_NGROUPS];
         pthread_mutex_unlock(&X->mu);
         memset(sites, 0, sizeof(sites));
-        for(i = 0; i < g->n; i++) if(g->launched[i]) { ls[nl] = g->slot[i]; li[nl] = i; nl++; }
+        for(i = 0; i < g->n; i++) if(g->launched[i] && !g->single[i]) { ls[nl] = g->slot[i]; li[nl] = i; nl++; }
         ta = now_s(); g_col_phase = 1;
-        if(nl && X->calls) { uint32_t keys[MDK_GROUP]; for(i = 0; i < nl; i++) keys[i] = g->ch[li[i]].index; rc = md_dev_calls_group(dev, ls, keys, nl, rcs); }
-        else if(nl) rc = md_dev_download_group(dev, ls, nl, st, rcs);
+        switch(X->sink) {
+        case SINK_BIAS:      /* (a chunk the host prepared was counted by a launch of its own: its slot's stream is waited for) */
+            for(i = 0; i < g->n && !rc; i++) if(g->launched[i] && g->single[i]) rc = md_dev_slot_sync(dev, g->slot[i]);
+            if(nl && !rc) rc = md_dev_mbias_collect(dev, ls, nl, rcs);
+            break;
+        case SINK_CALLS:
+            if(nl) { uint32_t keys[MDK_GROUP]; for(i = 0; i < nl; i++) keys[i] = g->ch[li[i]].index; rc = md_dev_calls_group(dev, ls, keys, nl, rcs); }
+            break;
+        default:
+            if(nl) rc = md_dev_download_group(dev, ls, nl, st, rcs);
+        }
         g_col_phase = 2;
         if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); xp_fail(X, MDK_RC_DEVICE); break; }
         for(i = 0; i < nl && !bad; i++) {
@@ -177,8 +189,9 @@ static void *collector_main(void *arg) {
                 static int told = 0;
                 if(!told) { told = 1; fprintf(stderr, "[mdk] note: a chunk holds a read name with more records than the device preparation handles (secondary/supplementary-rich or amplicon-like data); such chunks are prepared on the host, which is slower\n"); }
                 rc = mdk_plan_host_prepare_from(p, &g->ch[k], dev, g->slot[k]);
-                if(!rc) rc = md_dev_submit(dev, g->slot[k], &g->ch[k].batch);
-                if(!rc && X->calls) { int rc1 = 0; rc = md_dev_calls_group(dev, &g->slot[k], &g->ch[k].index, 1, &rc1); if(!rc) rc = rc1; }
+                if(!rc) rc = X->sink == SINK_BIAS ? md_dev_mbias_submit(dev, g->slot[k], &g->ch[k].batch) : md_dev_submit(dev, g->slot[k], &g->ch[k].batch);
+                if(!rc && X->sink == SINK_BIAS) rc = md_dev_slot_sync(dev, g->slot[k]);
+                else if(!rc && X->sink == SINK_CALLS) { int rc1 = 0; rc = md_dev_calls_group(dev, &g->slot[k], &g->ch[k].index, 1, &rc1); if(!rc) rc = rc1; }
                 else if(!rc) rc = md_dev_download(dev, g->slot[k], &st[i]);
                 X->n_host_prep++;
             }
@@ -189,7 +202,7 @@ static void *collector_main(void *arg) {
         }
         X->w_down += now_s() - ta;
         if(bad) break;
-        if(X->calls) { g_col_phase = 0; pthread_mutex_lock(&X->mu); g->n = 0; g->state = G_FREE; X->n_col++; pthread_cond_broadcast(&X->cv); pthread_mutex_unlock(&X->mu); continue; }      /* the rows stay on the device */
+        if(X->sink != SINK_TEXT) { g_col_phase = 0; pthread_mutex_lock(&X->mu); g->n = 0; g->state = G_FREE; X->n_col++; pthread_cond_broadcast(&X->cv); pthread_mutex_unlock(&X->mu); continue; }      /* the rows stay on the device */
         ta = now_s();
         g_col_phase = 3;
         for(i = 0; i < g->n; i++) if(emitter_push_lazy(X->em, &g->ch[i], &sites[i])) { xp_fail(X, X->em->failed ? MDK_RC_OUTPUT : MDK_RC_DEVICE); bad = 1; break; }
@@ -235,14 +248,16 @@ MDK_LOCAL void session_geometry(md_dev_cfg *cfg) {
 }
 
 /* extract_main's pipeline; S != NULL: a session's run -- no output files, no emitter, every collected group compacted into calls on S's device
- * handle (opened at the first run, reset before every later one), handed over in *out */
-static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
+ * handle (opened at the first run, reset before every later one), handed over in *out.  mbias (a session's only): the command line is mbias_main's, the
+ * groups are launched with md_dev_mbias_group and leave nothing but their status blocks, and the run ends with the histogram's table (md_dev_bias_finish) */
+static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int mbias) {
     mdk_plan *p = NULL; md_dev *dev = NULL; xpipe *X = NULL; int rc, ret = 0, more = 1, i, g_i; xopen dop; pthread_t cth, rth, preg; int cth_ok = 0, rth_ok = 0, preg_ok = 0; emitter em;
     double T0 = now_s(), t_open, t_dev, w_next = 0, w_sub = 0, w_group = 0, w_ref = 0, w_rel = 0, ta; uint64_t n_chunks = 0; int32_t ref_t0, ref_t1;
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] entered at epoch %.3f\n", ts.tv_sec + 1e-9 * ts.tv_nsec); }
     if(argc > 2 && !S) hip_warm_up();
     memset(&dop, 0, sizeof(dop)); memset(&em, 0, sizeof(em));
-    rc = plan_open_ex(argc, argv, &p, S ? session_options : xopen_start, &dop);
+    if(mbias) { rc = mdk_plan_open_mbias(argc, argv, &p); if(!rc && p) { mdk_plan_dev_cfg(p, &dop.d.cfg); session_geometry(&dop.d.cfg); } }
+    else rc = plan_open_ex(argc, argv, &p, S ? session_options : xopen_start, &dop);
     t_open = now_s() - T0;
     if(rc != 0 || !p) { if(dop.started) { pthread_join(dop.th, NULL); if(dop.d.dev) md_dev_close(dop.d.dev); } return rc; }
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] resident after plan open %.0f MB\n", rss_mb(0));
@@ -263,11 +278,12 @@ static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
     if(p->dev_prep) mdk_plan_attach_device(p, dev);      /* from here on the device inflates pieces of the file too */
     X = calloc(1, sizeof(*X));
     if(X) X->ref_state = calloc((size_t)p->bam->n_targets + 1, sizeof(int));
-    if(X && S) {     /* the session's sink: the calls configuration is the text post-pass's */
+    if(X && mbias) X->sink = SINK_BIAS;
+    else if(X && S) {     /* the session's sink: the calls configuration is the text post-pass's */
         md_calls_cfg cc; memset(&cc, 0, sizeof(cc));
         cc.min_depth = p->o.min_depth; cc.merge = p->o.merge; cc.min_opposite_depth = p->o.min_opp_depth > 0 ? p->o.min_opp_depth : 0; cc.max_variant_frac = p->o.max_variant_frac;
         for(i = 0; i < 3; i++) cc.ctx_on[i] = p->o.ctx_on[i];
-        X->calls = 1;
+        X->sink = SINK_CALLS;
         if(md_dev_calls_begin(dev, &cc)) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); free(X->ref_state); free(X); mdk_plan_detach_device(p); mdk_plan_close(p); return MDK_RC_DEVICE; }
     }
     if(!X || !X->ref_state || (!S && emitter_start(&em, p, emit_threads(p)))) { if(X) free(X->ref_state); free(X); mdk_plan_detach_device(p); if(!S) md_dev_close(dev); mdk_plan_close(p); return -5; }
@@ -304,12 +320,13 @@ static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
             if(rc == 2) break;
             if(rc < 0) { ret = rc == -5 ? -5 : -4; break; }
             if(rc == 0) { more = 0; break; }
-            g->launched[g->n] = 0; g->inplace[g->n] = 0;
+            g->launched[g->n] = 0; g->inplace[g->n] = 0; g->single[g->n] = 0;
+            if(mbias && (c->skipped & MDK_CHUNK_NOREF)) { ret = -4; break; }      /* as mbias_main: the reference's worker gives up here (MBias.c:150-155,543) */
             if(!c->skipped) {
                 ta = now_s(); rc = c->prep ? 0 : ref_wait(X, c->tid); w_ref += now_s() - ta;       /* (raw records can cross the link before the contig's bases have) */
                 ta = now_s(); g_up_phase = 6;
                 g->inplace[g->n] = 0;
-                if(!rc) { if(c->prep) { rc = md_dev_upload_raw_inplace(dev, g->slot[g->n], &c->raw); if(rc > 0) { g->inplace[g->n] = 1; rc = 0; } } else rc = md_dev_upload(dev, g->slot[g->n], &c->batch); }
+                if(!rc) { if(c->prep) { rc = md_dev_upload_raw_inplace(dev, g->slot[g->n], &c->raw); if(rc > 0) { g->inplace[g->n] = 1; rc = 0; } } else if(mbias) { rc = md_dev_mbias_submit(dev, g->slot[g->n], &c->batch); g->single[g->n] = 1; } else rc = md_dev_upload(dev, g->slot[g->n], &c->batch); }
                 w_sub += now_s() - ta; g_up_phase = 3;
                 if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
                 g->launched[g->n] = 1;
@@ -319,13 +336,13 @@ static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
         if(ret) break;
         {   /* one launch per kernel for the group's chunks */
             int ls[MDK_GROUP], nl = 0;
-            for(i = 0; i < g->n; i++) if(g->launched[i]) ls[nl++] = g->slot[i];
+            for(i = 0; i < g->n; i++) if(g->launched[i] && !g->single[i]) ls[nl++] = g->slot[i];
             ta = now_s(); g_up_phase = 7;
             for(i = 0, rc = 0; i < g->n && !rc; i++) if(g->launched[i] && g->ch[i].prep) rc = ref_wait(X, g->ch[i].tid);
             w_ref += now_s() - ta;
             if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; }
             g_up_phase = 8;
-            if(nl) { ta = now_s(); rc = md_dev_launch_group(dev, ls, nl); w_sub += now_s() - ta; if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; } }
+            if(nl) { ta = now_s(); rc = mbias ? md_dev_mbias_group(dev, ls, nl) : md_dev_launch_group(dev, ls, nl); w_sub += now_s() - ta; if(rc) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); ret = MDK_RC_DEVICE; break; } }
         }
         g->n_held = g->n; g->held = 0;
         for(i = 0; i < g->n; i++) { g->rel_slot[i] = (g->launched[i] && g->ch[i].prep && !g->inplace[i]) ? g->slot[i] : -1; g->rel_ch[i] = g->ch[i]; if(g->rel_slot[i] >= 0 && !getenv("MDK_NO_EARLY_RELEASE")) g->held = 1; }
@@ -344,12 +361,20 @@ static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
     if(rth_ok) pthread_join(rth, NULL);
     if(preg_ok) pthread_join(preg, NULL);
     if(!ret) ret = X->ret;
+    if(ret && S) (void)md_dev_sync(dev);      /* a session's run that ends early: what its groups queued (copies from the slabs, kernels over the pieces) has run before the plan gives that memory back */
     if(!S) { double tw = now_s(); emitter_stop(&em); X->w_emit += now_s() - tw; }
     if(em.failed && !ret) ret = MDK_RC_OUTPUT;
     if(getenv("MDK_HOST_PROFILE")) { double rs = 0; uint64_t rc2 = 0, rb = 0; md_host_profile(&rs, &rc2, &rb); fprintf(stderr, "[mdk main] staging blocks registered: %" PRIu64 " (%.0f MB) in %.3fs; %" PRIu64 " chunks in %" PRIu64 " group launches\n", rc2, rb / 1048576.0, rs, n_chunks, X->n_up); }
     if(getenv("MDK_HOST_PROFILE")) { char pt[1024]; if(md_dev_profile_text(pt, sizeof(pt)) == 0) fprintf(stderr, "[mdk hip] host threads inside the device library: %s\n", pt); }
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] plan open %.3fs, device ready at %.3fs, uploader: wait-for-chunk %.3fs wait-for-reference %.3fs wait-for-group %.3fs submit %.3fs wait-for-uploads %.3fs; collector: download %.3fs emit %.3fs, total %.3fs; chunks prepared on the host after all: %d\n", t_open, t_dev, w_next, w_ref, w_group, w_sub, w_rel, X->w_down, X->w_emit, now_s() - T0, X->n_host_prep);
-    if(S) {          /* the rows, in schedule order, handed over with the contig names; the handle's calls state is finished either way */
+    if(mbias) {      /* the table, the dense histogram and -- from the histogram read back with the row count -- the bounds the command suggests */
+        md_bias_set *set = NULL; const int frc = ret ? 0 : md_dev_bias_finish(dev, &set);
+        if(frc == MDK_ERR_STRAND0) { fprintf(stderr, "Can't determine the strand of a read!\n"); abort(); }
+        if(getenv("MDK_HOST_PROFILE") && set) fprintf(stderr, "[mdk main] mbias: %d chunks counted through the single-chunk path after their group launch\n", md_bias_set_redone(set));
+        ret = session_result(ret, frc, p, sizeof(mdk_bias), set, set ? md_bias_set_count(set) : 0, out);
+        if(ret) md_bias_set_free(set);
+        else { mdk_bias *b = *out; md_mbias hist; b->len = md_bias_set_len(set); b->redone = md_bias_set_redone(set); if(md_bias_set_hist(set, &hist) || mdk_mbias_suggest(&hist, b->bounds, b->has)) { mdk_bias_free(b); *out = NULL; ret = MDK_RC_DEVICE; } }
+    } else if(S) {          /* the rows, in schedule order, handed over with the contig names; the handle's calls state is finished either way */
         md_calls_set *set = NULL; const int frc = md_dev_calls_finish(dev, &set);
         ret = session_result(ret, frc, p, sizeof(mdk_calls), set, md_calls_set_count(set), out);
         if(ret) md_calls_set_free(set);
@@ -365,6 +390,9 @@ static int extract_run(int argc, char *argv[], mdk_session *S, void **out) {
       if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] device closed in %.3fs, plan (slabs, reference, mapped file) in %.3fs\n", td - tc, now_s() - td); }
     return ret;
 }
+
+static int extract_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, 0); }
+MDK_LOCAL int session_mbias_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, 1); }
 
 int extract_main(int argc, char *argv[]) {
     { int rk = 0, wd = 1, m = ranks_from_env(&rk, &wd); if(m < 0) return -1; if(m > 0) return extract_ranks(argc, argv, rk, wd); }       /* one process per GPU (mdk_ranks.c) */

@@ -104,7 +104,24 @@ static int strand_len(const md_mbias *h, int strand) {
     return 0;
 }
 
-static int svg_of_strand(const char *opref, int strand, const series s[2], int len, int which, int sugg[4]) {
+/* the inclusion bounds of every strand that has a call: bounds[4 * strand ..] = read 1 left, right, read 2 left, right (what the report prints
+ * as --OT a,b,c,d ...), has[strand] = 1; zeros for a strand without calls */
+int mdk_mbias_suggest(const md_mbias *h, int bounds[16], int has[4]) {
+    int strand, r;
+    if(!h || !bounds || !has || (h->len > 0 && !h->count)) return -1;
+    memset(bounds, 0, 16 * sizeof(int)); memset(has, 0, 4 * sizeof(int));
+    for(strand = 0; strand < 4; strand++) {
+        const int len = strand_len(h, strand); series s[2];
+        if(!len) continue;
+        for(r = 0; r < 2; r++) { s[r].row = h->count; s[r].col = strand * 4 + 2 * r; s[r].len = h->len; }
+        suggest(&s[0], len, &bounds[4 * strand], &bounds[4 * strand + 1]);
+        suggest(&s[1], len, &bounds[4 * strand + 2], &bounds[4 * strand + 3]);
+        has[strand] = 1;
+    }
+    return 0;
+}
+
+static int svg_of_strand(const char *opref, int strand, const series s[2], int len, int which, const int sugg[4]) {
     char *name = xmalloc(strlen(opref) + 16); FILE *f; double ymin, ymax, span; int first[2] = {len, len}, has[2] = {0, 0}, xmax, q, r, j, n, step, labelled = 0;
     sprintf(name, "%s_%s.svg", opref, ABBREV[strand]);
     f = fopen(name, "w");
@@ -147,8 +164,6 @@ static int svg_of_strand(const char *opref, int strand, const series s[2], int l
     }
     for(r = 0; r < 2; r++) if(has[r]) draw_series(f, &s[r], len, first[r], xmax, ymin, ymax, COLOUR[r]);
     for(r = 0; r < 2; r++) if(has[r]) draw_line(f, &s[r], len, first[r], xmax, ymin, ymax, COLOUR[r]);
-    suggest(&s[0], len, &sugg[0], &sugg[1]);
-    suggest(&s[1], len, &sugg[2], &sugg[3]);
     if(sugg[0] + sugg[1] + sugg[2] + sugg[3]) {
         fprintf(f, "<text x=\"%i\" y=\"%i\" text-anchor=\"end\">--%s %i,%i,%i,%i</text>\n", 2 * MARGIN + AREA - 10, 2 * MARGIN + AREA - 10, ABBREV[strand], sugg[0], sugg[1], sugg[2], sugg[3]);
         for(j = 0; j < 4; j++) if(sugg[j]) bound_marker(f, sugg[j], xmax, COLOUR[j >> 1]);
@@ -166,8 +181,10 @@ int mdk_mbias_report(const md_mbias *h, const char *opref, int svg, int txt, int
     int strand, q, r, printing = 0;
     if(!h || (h->len > 0 && !h->count) || (svg && !opref)) return -1;
     if(svg) {
+        int bounds[16], has[4];
+        if(mdk_mbias_suggest(h, bounds, has)) return -1;
         for(strand = 0; strand < 4; strand++) {
-            int len = strand_len(h, strand), sugg[4]; series s[2];
+            int len = strand_len(h, strand); const int *sugg = bounds + 4 * strand; series s[2];
             if(!len) continue;
             for(r = 0; r < 2; r++) { s[r].row = h->count; s[r].col = strand * 4 + 2 * r; s[r].len = h->len; }
             if(svg_of_strand(opref, strand, s, len, which, sugg)) { fprintf(stderr, "[mdk] cannot write %s_%s.svg\n", opref, ABBREV[strand]); return -3; }

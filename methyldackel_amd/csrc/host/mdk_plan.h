@@ -146,6 +146,8 @@ MDK_LOCAL void session_device(mdk_session *S, devopen_t *d);   /* the session's 
 typedef struct { void *set; int64_t n; int n_contigs; char **names; } mdk_result;
 struct mdk_calls { mdk_result r; };
 struct mdk_reads { mdk_result r; int64_t n_bytes; };
+struct mdk_bias { mdk_result r; int len, redone, bounds[16], has[4]; };
+MDK_LOCAL int session_mbias_run(int argc, char *argv[], mdk_session *S, void **out);      /* (mdk_extract.c) extract_run's pipeline with the histogram as its sink */
 typedef int (*session_run_fn)(int argc, char *argv[], mdk_session *S, void **out);
 MDK_LOCAL int session_run(mdk_session *s, int argc, char *argv[], void **out, size_t size, session_run_fn run);     /* mdk_session_<command>: argument check, the run, an empty result of `size` bytes where it made none */
 /* the end of a run: `ret` its code so far, `frc` what md_dev_{calls,reads}_finish gave.  *out = a new result of `size` bytes (an mdk_result first) that owns

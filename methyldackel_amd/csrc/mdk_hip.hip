@@ -732,7 +732,7 @@ __global__ __launch_bounds__(PACK_WG) void k_sites_pack(const KPack K) {
 #define MB_LQ 512
 
 __device__ __forceinline__ void mbias_seg(const KParams &P, const md_seg &g, int T0, int T1,
-                                          const uint16_t *listC, int nC, const uint16_t *listG, int nG, uint32_t *lh) {
+                                          const uint16_t *listC, int nC, const uint16_t *listG, int nG, uint32_t *lh, int hist_lq) {
     const int send = g.rpos + (int)g.len;
     if(g.rpos >= T1 || send <= T0) return;
     const int strand = g.sf & MDK_SF_STRAND;
@@ -758,19 +758,15 @@ __device__ __forceinline__ void mbias_seg(const KParams &P, const md_seg &g, int
         if(odd) { if(bq == 2) un = 0; else if(bq == 8) un = 1; else continue; }
         else { if(bq == 4) un = 0; else if(bq == 1) un = 1; else continue; }
         const int idx = q * 16 + col + un;
-        if(q < P.hist_lq) atomicAdd(&lh[idx], 1u); else atomicAdd(&P.hist[idx], 1u);
+        if(q < hist_lq) atomicAdd(&lh[idx], 1u); else atomicAdd(&P.hist[idx], 1u);
     }
 }
 
-__global__ __launch_bounds__(WG, 8) void k_mbias(const KParams P) {
-    extern __shared__ __align__(16) uint32_t lds[];
+// one tile of one chunk: context lists, the histogram rows [0, hist_lq) of the chunk's calls in LDS, flushed once (non-zero entries only)
+__device__ __forceinline__ void mbias_tile(const KParams &P, int t, int hist_lq, uint32_t *lds, int *wsum) {
     const int TILE = P.tile, PER = TILE / WG;
     uint16_t *listC = (uint16_t *)lds, *listG = listC + TILE;
     uint32_t *lh = lds + TILE;
-    __shared__ int wsum[WAVES];
-    const int b = blockIdx.x;
-    const int t = (b & 7) * P.nper + (b >> 3);
-    if(t >= P.ntiles) return;
     const int64_t T0 = P.beg + (int64_t)t * TILE;
     const int64_t T1 = (T0 + TILE < P.end) ? T0 + TILE : P.end;
     const int tlen = (int)(T1 - T0);
@@ -779,16 +775,55 @@ __global__ __launch_bounds__(WG, 8) void k_mbias(const KParams P) {
     if(te.last <= te.first) { te.first = 0; te.last = 0; }
     int code[PERMAX];
     load_codes(P, T0, tlen, PER, tid, code);
-    const int nh = 16 * P.hist_lq;
+    const int nh = 16 * hist_lq;
     for(int i = tid; i < nh; i += WG) lh[i] = 0;
     int nC, nG;
     build_lists(P, PER, tid, lane, wave, code, listC, listG, wsum, nC, nG);
     for(int r = te.first + tid; r < te.last; r += WG) {
         const md_seg g = P.seg[r];
-        mbias_seg(P, g, (int)T0, (int)T1, listC, nC, listG, nG, lh);
+        mbias_seg(P, g, (int)T0, (int)T1, listC, nC, listG, nG, lh, hist_lq);
     }
     __syncthreads();
     for(int i = tid; i < nh; i += WG) { const uint32_t v = lh[i]; if(v) atomicAdd(&P.hist[i], v); }
+}
+
+__global__ __launch_bounds__(WG, 8) void k_mbias(const KParams P) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    __shared__ int wsum[WAVES];
+    const int b = blockIdx.x;
+    const int t = (b & 7) * P.nper + (b >> 3);
+    if(t >= P.ntiles) return;
+    mbias_tile(P, t, P.hist_lq, lds, wsum);
+}
+
+// The histogram of up to MAXM chunks in ONE launch, queued directly behind their preparation (md_dev_mbias_group): what the host used to read
+// from the chunk's status block before it launched k_mbias, every workgroup reads there itself.  A histogram add cannot be taken back, so a
+// chunk adds either all of its counts or none: when its preparation did not end cleanly (a malformed record, a read of unknown strand, a
+// read-name chain for the host, more segments than the slot's array holds) or its longest admitted read has more positions than the
+// histogram has rows, every workgroup of the chunk leaves and the chunk's status says MB_SKIPPED -- the host sends it through the single-chunk
+// path when it collects the group.  Rows kept in LDS: the chunk's longest read, at most what the launch reserved (lds_rows).
+#define MB_COUNTED 2u
+#define MB_SKIPPED 1u
+struct KMbMulti { int n, nper, hist_cap, lds_rows; int tstart[MAXM + 1]; uint32_t segcap[MAXM]; SlotStatus *st[MAXM]; KParams P[MAXM]; };
+__global__ __launch_bounds__(WG, 8) void k_mbias_multi(const KMbMulti M) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    __shared__ int wsum[WAVES];
+    const int b = blockIdx.x;
+    const int tg = (b & 7) * M.nper + (b >> 3);
+    if(tg >= M.tstart[M.n]) return;
+    int j = 0;
+    while(j + 1 < M.n && tg >= M.tstart[j + 1]) j++;
+    const int t = tg - M.tstart[j];
+    SlotStatus *S = M.st[j];
+    const PrepCounters &c = S->pc;
+    const uint32_t maxlq = c.max_lq;
+    const bool clean = !c.malformed && !c.strand0 && !c.fallback && c.n_segs <= M.segcap[j] && maxlq <= (uint32_t)M.hist_cap;
+    if(t == 0 && threadIdx.x == 0) S->pad = clean ? MB_COUNTED : MB_SKIPPED;
+    if(!clean) return;
+    int rows = (int)((maxlq + 7) & ~7u);
+    if(rows > M.lds_rows) rows = M.lds_rows;
+    if(rows > M.hist_cap) rows = M.hist_cap;
+    mbias_tile(M.P[j], t, rows, lds, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1079,7 +1114,8 @@ extern "C" void md_dev_close(md_dev *h) {
     if(!h) return;
     side_join(false);
     (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
+    mdk_debug_state("md_dev_close, before");
+    { const hipError_t er = hipDeviceSynchronize(); if(er != hipSuccess && getenv("MDK_DEBUG_STATE")) fprintf(stderr, "[mdk state] md_dev_close: hipDeviceSynchronize: %s\n", hipGetErrorString(er)); }
     for(auto &s : h->slots) {
         slot_buffers_release(s);
         if(s.e0) (void)hipEventDestroy(s.e0); if(s.e1) (void)hipEventDestroy(s.e1); if(s.k0) (void)hipEventDestroy(s.k0); if(s.k1) (void)hipEventDestroy(s.k1);
@@ -1098,6 +1134,7 @@ extern "C" void md_dev_close(md_dev *h) {
     for(md_region *p : h->d_runs) if(p) (void)hipFree(p);
     for(size_t t = 0; t < h->ref.size(); t++) ref_release(h, t);
     delete h;
+    mdk_debug_state("md_dev_close, after");
 }
 
 // An idle handle back to what md_dev_open left (a resident service runs one command after another on it): every slot's buffers, the
@@ -1111,6 +1148,7 @@ extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     if(ns != h->n_slots || cfg->n_streams != h->cfg.n_streams) return fail(MDK_ERR_ARG, "md_dev_reset: another number of slots or streams needs md_dev_close + md_dev_open", hipSuccess);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
+    mdk_debug_state("md_dev_reset, before");
     for(size_t t = 0; t < h->ref.size(); t++) ref_release(h, t);
     h->ref.clear(); h->refcode.clear(); h->reflen.clear(); h->ref_carved.clear(); h->refcap.clear();
     for(uint32_t *p : h->mapbits) if(p) (void)hipFree(p);
@@ -1119,7 +1157,7 @@ extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     h->d_runs.clear(); h->n_runs.clear(); h->has_runs.clear();
     memset(&h->prep, 0, sizeof(h->prep)); h->prep_set = false;
     if(h->d_hist) (void)hipFree(h->d_hist);
-    h->d_hist = nullptr; h->hist_cap = 0; h->hist_len = 0; h->h_hist.clear();
+    h->d_hist = nullptr; h->hist_cap = 0; h->hist_len = 0; h->h_hist.clear(); h->mb_redone = 0;
     if(h->calls) { calls_state_free(h); }
     h->no_pack = false;
     reads_state_free(h); h->reads_on = false;
@@ -1130,6 +1168,7 @@ extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
         s = f;
     }
     h->d_status.release(); h->h_status.release();
+    mdk_debug_state("md_dev_reset, released");
     arena_restart_if_idle(h->device); harena_restart_if_idle();
     if(h->d_status.need((size_t)h->n_slots) || h->h_status.need((size_t)h->n_slots)) return MDK_ERR_NOMEM;
     HIPCHK(hipMemset(h->d_status.p, 0, sizeof(SlotStatus) * (size_t)h->n_slots));
@@ -1417,6 +1456,9 @@ extern "C" int md_dev_submit(md_dev *h, int slot, const md_read_batch *b) {
 // ------------------------------------------------------------------------------------------------
 // mbias entry points
 // ------------------------------------------------------------------------------------------------
+// (h->mb_mu held) room for `rows` rows.  Growing drains the device first: no histogram kernel is in flight while the rows move, and none can
+// be launched meanwhile -- every launch takes mb_mu.  A chunk of a group launch that ran against the smaller histogram and did not fit has
+// added nothing (k_mbias_multi) and comes through here again when its group is collected.
 static int hist_reserve(md_dev *h, int rows) {
     if(rows <= h->hist_cap) return 0;
     int cap = h->hist_cap ? h->hist_cap : 1024;
@@ -1431,16 +1473,12 @@ static int hist_reserve(md_dev *h, int rows) {
     h->d_hist = d; h->hist_cap = cap;
     return 0;
 }
-
-extern "C" int md_dev_mbias_submit(md_dev *h, int slot, const md_read_batch *b) {
-    int rc = md_dev_upload(h, slot, b);
-    if(rc) return rc;
-    Slot *s = get_slot(h, slot);
-    int maxlq = 0;
-    for(int i = 0; i < b->n_segs; i++) if((int)b->seg[i].l_qseq > maxlq) maxlq = (int)b->seg[i].l_qseq;
+// (h->mb_mu held) the histogram kernel of one prepared chunk on the slot's stream
+static int mbias_launch_one(md_dev *h, Slot *s, int maxlq) {
+    int rc;
     if((rc = hist_reserve(h, maxlq > 1 ? maxlq : 1)) != 0) return rc;
     if(maxlq > h->hist_len) h->hist_len = maxlq;
-    if(s->ntiles <= 0 || b->n_segs == 0) return 0;
+    if(s->ntiles <= 0 || s->n_segs <= 0) return 0;
     KParams P; if((rc = fill_kparams(h, s, P)) != 0) return rc;
     P.mbias = 1; P.hist = h->d_hist;
     P.hist_lq = maxlq < MB_LQ ? (maxlq + 7) & ~7 : MB_LQ; if(P.hist_lq > h->hist_cap) P.hist_lq = h->hist_cap;
@@ -1448,6 +1486,16 @@ extern "C" int md_dev_mbias_submit(md_dev *h, int slot, const md_read_batch *b) 
     hipLaunchKernelGGL(k_mbias, dim3(P.nper * 8), dim3(WG), lds, s->stream, P);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+extern "C" int md_dev_mbias_submit(md_dev *h, int slot, const md_read_batch *b) {
+    int rc = md_dev_upload(h, slot, b);
+    if(rc) return rc;
+    Slot *s = get_slot(h, slot);
+    int maxlq = 0;
+    for(int i = 0; i < b->n_segs; i++) if((int)b->seg[i].l_qseq > maxlq) maxlq = (int)b->seg[i].l_qseq;
+    std::lock_guard<std::mutex> lk(h->mb_mu);
+    return mbias_launch_one(h, s, maxlq);
 }
 
 // The same from the chunk's raw records: the device prepares them (no pairing: md_prep_cfg.no_pairing) and tells how long the longest
@@ -1466,17 +1514,8 @@ static int mbias_finish(md_dev *h, Slot *s) {
         rc = prep_outcome(h, s);
     }
     if(rc) return rc;
-    const int maxlq = (int)s->h_st.p->pc.max_lq;
-    if((rc = hist_reserve(h, maxlq > 1 ? maxlq : 1)) != 0) return rc;
-    if(maxlq > h->hist_len) h->hist_len = maxlq;
-    if(s->ntiles <= 0 || s->n_segs <= 0) return 0;
-    KParams P; if((rc = fill_kparams(h, s, P)) != 0) return rc;
-    P.mbias = 1; P.hist = h->d_hist;
-    P.hist_lq = maxlq < MB_LQ ? (maxlq + 7) & ~7 : MB_LQ; if(P.hist_lq > h->hist_cap) P.hist_lq = h->hist_cap;
-    const size_t lds = (size_t)s->tile * 4 + (size_t)P.hist_lq * 16 * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_mbias, dim3(P.nper * 8), dim3(WG), lds, s->stream, P);
-    HIPCHK(hipGetLastError());
-    return 0;
+    std::lock_guard<std::mutex> lk(h->mb_mu);
+    return mbias_launch_one(h, s, (int)s->h_st.p->pc.max_lq);
 }
 extern "C" int md_dev_mbias_submit_raw(md_dev *h, int slot, const md_raw_batch *b) {
     if(!h || !h->prep_set || !h->prep.no_pairing) return fail(MDK_ERR_ARG, "md_dev_mbias_submit_raw: md_dev_set_prep with no_pairing first", hipSuccess);
@@ -1493,6 +1532,110 @@ extern "C" int md_dev_mbias_submit_raw(md_dev *h, int slot, const md_raw_batch *
     return 0;
 }
 
+// Up to MAXM uploaded chunks of raw records: their preparation and their histogram, one launch per kernel on the first slot's stream, and the
+// copy of their status blocks behind it.  Nothing is waited for: what k_mbias used to be told by the host, k_mbias_multi reads on the device.
+// LDS is reserved for the longest read the run has met so far (MB_LQ rows until a group has been collected, never more).
+extern "C" int md_dev_mbias_group(md_dev *h, const int *slots, int n) {
+    if(!h || !slots || n < 1 || n > MAXM) return fail(MDK_ERR_ARG, "md_dev_mbias_group: 1..8 slots", hipSuccess);
+    if(!h->prep_set || !h->prep.no_pairing) return fail(MDK_ERR_ARG, "md_dev_mbias_group: md_dev_set_prep with no_pairing first", hipSuccess);
+    ProfScope pf(PF_LAUNCH);
+    HIPCHK(hipSetDevice(h->device));
+    static_assert(sizeof(KMbMulti) <= 4096, "kernel arguments are limited to 4 KiB");
+    KMbMulti M; memset(&M, 0, sizeof(M));
+    Slot *s0 = get_slot(h, slots[0]); if(!s0) return MDK_ERR_ARG;
+    hipStream_t st = s0->stream;
+    for(int i = 0; i < n; i++) {
+        Slot *s = get_slot(h, slots[i]);
+        if(!s || !s->uploaded || !s->raw_layout || !s->prep_pending || s->mb_pending) return fail(MDK_ERR_ARG, "md_dev_mbias_group: every slot freshly uploaded with md_dev_upload_raw", hipSuccess);
+        for(int k = 0; k < i; k++) if(slots[k] == slots[i]) return fail(MDK_ERR_ARG, "md_dev_mbias_group: a slot is listed twice", hipSuccess);
+        if(s->tile != s0->tile) return fail(MDK_ERR_ARG, "md_dev_mbias_group: slots of different tile size", hipSuccess);
+        if((size_t)s->tid >= h->ref.size() || !h->ref[s->tid]) { snprintf(g_err, sizeof(g_err), "reference for tid %d not uploaded", s->tid); return MDK_ERR_NOREF; }
+    }
+    std::lock_guard<std::mutex> lk(h->mb_mu);
+    { const int rc = hist_reserve(h, 1); if(rc) return rc; }
+    int total = 0; Slot *ss[MAXM];
+    for(int i = 0; i < n; i++) {
+        Slot *s = ss[i] = get_slot(h, slots[i]);
+        int rc = fill_kparams(h, s, M.P[i]); if(rc) return rc;
+        M.P[i].mbias = 1; M.P[i].hist = h->d_hist;
+        M.tstart[i] = total; total += s->ntiles > 0 ? s->ntiles : 0;
+        M.segcap[i] = (uint32_t)std::min<size_t>(s->d_seg_in.cap, 0xffffffffu); M.st[i] = h->d_status.p + s->index;
+        if(s->fresh && s->stream != st) { HIPCHK(hipEventRecord(s->e0, s->stream)); HIPCHK(hipStreamWaitEvent(st, s->e0, 0)); }      // its upload comes first
+        s->fresh = false; s->run = st;
+    }
+    M.n = n; M.tstart[n] = total; M.nper = (total + 7) / 8; M.hist_cap = h->hist_cap;
+    const int met = std::max(h->hist_len, h->mb_hint);      // the longest read met so far: in this run, or -- the handle's runs mostly see one library -- in the run before
+    M.lds_rows = met > 0 ? std::min(MB_LQ, (met + 7) & ~7) : MB_LQ;
+    if(M.lds_rows > h->hist_cap) M.lds_rows = h->hist_cap;
+    { const int rc = enqueue_prep_group(h, ss, n, st); if(rc) return rc; }
+    if(total > 0) {
+        const size_t lds = (size_t)s0->tile * 4 + (size_t)M.lds_rows * 16 * sizeof(uint32_t);
+        // CpG only, one launch over all chunks (14.3 against 24.5 us per chunk of single launches).  With CHG / CHH on, a tile's workgroup is
+        // ~100 us of LDS and global atomics and a lone chunk's launch fills 0.64 of the device's workgroup slots: eight chunks in one launch
+        // ran 145 us per chunk against 105 us of single launches (k_mbias) -- there the chunks get a launch each, queued here all
+        // the same, still without a host wait
+        const bool dense = h->cfg.keepCHG || h->cfg.keepCHH;
+        if(!dense) hipLaunchKernelGGL(k_mbias_multi, dim3(M.nper * 8), dim3(WG), lds, st, M);
+        else for(int i = 0; i < n; i++) {
+            const int nt = M.tstart[i + 1] - M.tstart[i];
+            if(nt <= 0) continue;
+            KMbMulti M1; memset(&M1, 0, sizeof(M1));
+            M1.n = 1; M1.nper = (nt + 7) / 8; M1.hist_cap = M.hist_cap; M1.lds_rows = M.lds_rows; M1.tstart[1] = nt;
+            M1.segcap[0] = M.segcap[i]; M1.st[0] = M.st[i]; M1.P[0] = M.P[i];
+            hipLaunchKernelGGL(k_mbias_multi, dim3(M1.nper * 8), dim3(WG), lds, st, M1);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    for(int i = 0; i < n; i++) { HIPCHK(hipMemcpyAsync(ss[i]->h_st.p, h->d_status.p + ss[i]->index, sizeof(SlotStatus), hipMemcpyDeviceToHost, st)); ss[i]->launched = true; }
+    return 0;
+}
+
+// The host's end of a group launch: waits for it and reads the chunks' status blocks.  rc[i]: 0, or what the chunk's preparation reported
+// (MDK_ERR_PREP_HOST: the caller prepares it on the host and hands it to md_dev_mbias_submit; MDK_ERR_STRAND0; a malformed record) -- such a
+// chunk has added nothing.  A chunk the device skipped for want of room (segments, histogram rows) goes through the single-chunk path
+// here: its preparation again with the array it needs, the histogram grown with the device drained, k_mbias, and the wait for it.
+extern "C" int md_dev_mbias_collect(md_dev *h, const int *slots, int n, int *rc) {
+    if(!h || !slots || !rc || n < 1 || n > MAXM) return fail(MDK_ERR_ARG, "md_dev_mbias_collect", hipSuccess);
+    HIPCHK(hipSetDevice(h->device));
+    ProfScope pf(PF_FIN_WAIT);
+    for(int i = 0; i < n; i++) rc[i] = 0;
+    for(int i = 0; i < n; i++) {
+        Slot *s = get_slot(h, slots[i]);
+        if(!s || !s->launched || !s->raw_layout) return fail(MDK_ERR_ARG, "md_dev_mbias_collect: slot not launched by md_dev_mbias_group", hipSuccess);
+        HIPCHK(hipStreamSynchronize(s->run ? s->run : s->stream));
+    }
+    for(int i = 0; i < n; i++) {
+        Slot *s = get_slot(h, slots[i]);
+        s->launched = false;
+        const uint32_t verdict = s->h_st.p->pad;
+        bool again = false;
+        int r = prep_outcome(h, s);
+        if(r == MDK_ERR_PREP_REDO) {                   // more segments than the array held: the preparation is queued again on the slot's stream
+            again = true;
+            HIPCHK(hipMemcpyAsync(s->h_st.p, h->d_status.p + s->index, sizeof(SlotStatus), hipMemcpyDeviceToHost, s->stream));
+            HIPCHK(hipStreamSynchronize(s->stream));
+            r = prep_outcome(h, s);
+        }
+        if(!r && s->h_st.p->err) { snprintf(g_err, sizeof(g_err), "Can't determine the strand of a read!"); (void)hipMemset(s->d_err.p, 0, sizeof(int)); r = MDK_ERR_STRAND0; }
+        rc[i] = r;
+        if(r) continue;
+        const int maxlq = (int)s->h_st.p->pc.max_lq;
+        std::lock_guard<std::mutex> lk(h->mb_mu);
+        if(s->ntiles > 0 && s->n_segs > 0 && (again || verdict != MB_COUNTED)) {
+            if(!again && verdict != MB_SKIPPED) return fail(MDK_ERR_ARG, "md_dev_mbias_collect: the chunk's status holds no verdict of k_mbias_multi", hipSuccess);
+            const int r1 = mbias_launch_one(h, s, maxlq); if(r1) return r1;
+            HIPCHK(hipStreamSynchronize(s->stream));       // (the caller gives the chunk's records back once this returns)
+            h->mb_redone++;
+        } else {                                           // (counted, or nothing to count: the rows its longest read names exist either way, as after k_mbias)
+            const int r1 = hist_reserve(h, maxlq > 1 ? maxlq : 1); if(r1) return r1;
+            if(maxlq > h->hist_len) h->hist_len = maxlq;
+        }
+        s->busy = false;                               // its streams have been waited for and nothing was queued since
+    }
+    return 0;
+}
+extern "C" int md_dev_mbias_redone(const md_dev *h) { return h ? h->mb_redone : MDK_ERR_ARG; }
+
 extern "C" int md_dev_slot_sync(md_dev *h, int slot) {
     Slot *s = get_slot(h, slot);
     if(!s) return MDK_ERR_ARG;
@@ -1502,9 +1645,8 @@ extern "C" int md_dev_slot_sync(md_dev *h, int slot) {
     return 0;
 }
 
-extern "C" int md_dev_mbias_read(md_dev *h, md_mbias *out) {
-    if(!h || !out) return fail(MDK_ERR_ARG, "md_dev_mbias_read", hipSuccess);
-    HIPCHK(hipSetDevice(h->device));
+// every queued histogram kernel has run (the slots' deferred ones included); a read of unknown strand met by any of them is reported here
+int mbias_drain(md_dev *h) {
     for(Slot &o : h->slots) { const int rc = mbias_finish(h, &o); if(rc) return rc; }
     HIPCHK(hipDeviceSynchronize());
     for(auto &s : h->slots) {
@@ -1512,6 +1654,12 @@ extern "C" int md_dev_mbias_read(md_dev *h, md_mbias *out) {
         HIPCHK(hipMemcpy(&err, s.d_err.p, sizeof(int), hipMemcpyDeviceToHost));
         if(err) { snprintf(g_err, sizeof(g_err), "Can't determine the strand of a read!"); (void)hipMemset(s.d_err.p, 0, sizeof(int)); return MDK_ERR_STRAND0; }
     }
+    return 0;
+}
+extern "C" int md_dev_mbias_read(md_dev *h, md_mbias *out) {
+    if(!h || !out) return fail(MDK_ERR_ARG, "md_dev_mbias_read", hipSuccess);
+    HIPCHK(hipSetDevice(h->device));
+    { const int rc = mbias_drain(h); if(rc) return rc; }
     h->h_hist.assign((size_t)(h->hist_len > 0 ? h->hist_len : 1) * 16, 0u);
     if(h->hist_len > 0) HIPCHK(hipMemcpy(h->h_hist.data(), h->d_hist, (size_t)h->hist_len * 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     out->len = h->hist_len; out->count = h->h_hist.data();
@@ -1524,7 +1672,7 @@ extern "C" int md_dev_mbias_reset(md_dev *h) {
     for(Slot &o : h->slots) { const int rc = mbias_finish(h, &o); if(rc) return rc; }
     HIPCHK(hipDeviceSynchronize());
     if(h->d_hist) { HIPCHK(hipMemset(h->d_hist, 0, (size_t)h->hist_cap * 16 * sizeof(uint32_t))); HIPCHK(hipDeviceSynchronize()); }
-    h->hist_len = 0;
+    h->hist_len = 0; h->mb_redone = 0;
     return 0;
 }
 
@@ -1881,7 +2029,7 @@ MDK_HIDDEN void host_block_ensure_registered(const void *ptr) {
         lk.unlock();
         const auto t0 = std::chrono::steady_clock::now();
         bool ok; { MarkScope mk("hipHostRegister"); ok = hipHostRegister(base, len, hipHostRegisterDefault) == hipSuccess; }
-        if(!ok) (void)hipGetLastError();                             // a block that cannot be registered is uploaded pageable
+        if(!ok) { const hipError_t er = hipGetLastError(); if(getenv("MDK_DEBUG_STATE")) fprintf(stderr, "[mdk state] hipHostRegister(%p, %zu) failed: %s\n", (void *)base, len, hipGetErrorString(er)); }      // a block that cannot be registered is uploaded pageable
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         lk.lock();
         HostBlock k2{base, 0, 0};
@@ -1911,6 +2059,15 @@ extern "C" int md_host_register_all(md_dev *h, int threads) {
     for(auto &t : th) t.join();
     return (int)todo.size();
 }
+static void debug_state(const char *where) {
+    if(!getenv("MDK_DEBUG_STATE")) return;
+    int st[4] = {0, 0, 0, 0}; size_t nb = 0;
+    { std::lock_guard<std::mutex> lk(g_blocks_mu); nb = g_blocks.size(); for(const HostBlock &b : g_blocks) st[b.state & 3]++; }
+    Arena &A = g_arena[0]; std::lock_guard<std::mutex> lk(A.mu);
+    fprintf(stderr, "[mdk state] %s: handles %d, arena blocks %zu cur %zu used %zu live %ld, harena blocks %zu live %ld, host blocks %zu (unreg %d, busy %d, reg %d, failed %d)\n",
+            where, g_open_handles.load(), A.blocks.size(), A.cur, A.used, A.live, g_harena.blocks.size(), g_harena.live, nb, st[0], st[1], st[2], st[3]);
+}
+void mdk_debug_state(const char *where) { debug_state(where); }
 static std::atomic<int> g_want_pinned{1};
 extern "C" void md_host_set_pinned(int on) { g_want_pinned.store(on != 0); }
 extern "C" void *md_host_alloc(uint64_t bytes) {
@@ -1934,7 +2091,7 @@ extern "C" void md_host_free(void *q) {
             if(it->state == 1) { g_blocks_cv.wait(lk); continue; }          // somebody is registering it (or taking its registration away) right now
             if(it->state == 2) {                                            // the lock is given up while the runtime unpins the block: uploaders looking their blocks up do not queue behind it
                 it->state = 1; lk.unlock();
-                { MarkScope mk("hipHostUnregister"); (void)hipHostUnregister(p); }
+                { MarkScope mk("hipHostUnregister"); const hipError_t er = hipHostUnregister(p); if(er != hipSuccess) { (void)hipGetLastError(); if(getenv("MDK_DEBUG_STATE")) fprintf(stderr, "[mdk state] hipHostUnregister(%p) failed: %s\n", (void *)p, hipGetErrorString(er)); } }
                 lk.lock();
                 it = std::lower_bound(g_blocks.begin(), g_blocks.end(), key, block_less);
                 if(it != g_blocks.end() && it->base == p) g_blocks.erase(it);

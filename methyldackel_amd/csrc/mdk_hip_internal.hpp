@@ -146,6 +146,7 @@ struct md_dev {
     md_prep_cfg prep; bool prep_set = false; std::vector<uint32_t *> mapbits; std::vector<int64_t> maplen;
     std::vector<md_region *> d_runs; std::vector<int64_t> n_runs; std::vector<char> has_runs;       // -l runs kept for the read prefilter
     uint32_t *d_hist = nullptr; int hist_cap = 0, hist_len = 0; std::vector<uint32_t> h_hist;      // mbias: rows [q][16], q < hist_cap
+    std::mutex mb_mu; int mb_redone = 0, mb_hint = 0;     // mb_mu: d_hist, hist_cap and hist_len -- held while a histogram kernel is launched and while the histogram grows (a group's uploader and its collector are two threads); mb_redone: chunks of group launches that went through the single-chunk path; mb_hint: the longest read of the handle's last finished mbias run (kept across md_dev_reset: it sizes the LDS rows of a run's first groups)
     std::atomic<bool> scan_wide{getenv("MDK_SCAN_WIDE") && atoi(getenv("MDK_SCAN_WIDE")) > 0}; bool scan_wide_fixed = getenv("MDK_SCAN_WIDE") != nullptr;      // k_prep_scan's windows: wide for libraries with long read names (prep_outcome decides from the first chunks unless the environment has)
 };
 
@@ -209,6 +210,8 @@ MDK_HIDDEN int prep_kernels_init();           // mdk_prep.hip: its code object l
 MDK_HIDDEN void inflate_kernels_warm();
 MDK_HIDDEN hipStream_t mdk_piece_stream_take(int device);      // a low-priority stream for the device inflate (its own pool of hardware queues)
 MDK_HIDDEN hipStream_t mdk_stream_take(int device);       // a stream made ahead by md_dev_warm, or a new one      // mdk_inflate.hip: its code object loaded
+MDK_HIDDEN void mdk_debug_state(const char *where);      // MDK_DEBUG_STATE=1: the process-wide tables (open handles, carved memory, staging blocks) on stderr
+MDK_HIDDEN int mbias_drain(md_dev *h);         // mdk_hip.hip: every queued histogram kernel has run; MDK_ERR_STRAND0 when one met a read of unknown strand
 MDK_HIDDEN int enqueue_prep_group(md_dev *h, Slot *const *ss, int n, hipStream_t st);      // preparation kernels of up to MAXM uploaded raw slots, one launch each kernel
 // Session tables (mdk_calls.hip, mdk_reads.hip): ONE device allocation -- plain hipMalloc, not carved -- sliced into typed columns, every
 // column starting 256-byte aligned.  A run's tables are grown by doubling, never below their floor, with a copy of what they hold, and are

@@ -9,6 +9,8 @@
  * chunk take t microseconds per 1000 records on the "device" ("compute time" in the background, for the work balance between ranks).
  * perRead (tests/test_reads_cpu.py): a chunk's reads are selected from its records as the device selects them, and their counts are the
  * oracle's `perRead` lines for the same command line, in order (MDK_STANDIN_PERREAD); md_dev_reads_* keep the rows in host memory.
+ * mbias (tests/test_bias_cpu.py): the stand-in cannot count, so the histogram of the process's i-th mbias run is GIVEN -- the oracle's --noSVG
+ * table, $MDK_STANDIN_MBIAS/<i>.txt, added when the run's first chunk is submitted; md_dev_bias_finish restates k_bias_rows' order rule.
  *   build: gcc -O2 -shared -fPIC -Iinclude -o tools/_build/libmdk_dev_standin.so tools/dev_standin.c -lz -lpthread */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -37,6 +39,7 @@ typedef struct { uint32_t *kept; md_pr_count *cnt; int64_t n, cap; int pending; 
 struct md_dev { md_dev_cfg cfg; int n_slots; sslot *slot; long n_up; int handback; pthread_mutex_t mu; double busy_until; int us_per_krec;
                 md_calls_cfg ccfg; int calls_on; cchunk_t *cch; int n_cch, cap_cch;
                 md_prep_cfg prep; prslot_t *pr; int64_t pr_next;           /* pr_next: the oracle's perRead line the next kept read must match */
+                uint32_t *mb_hist; int mb_len, mb_loaded;                  /* mbias: the given histogram [q][16], its rows, whether this run's table is in */
                 int reads_on; int32_t *r_contig, *r_pos, *r_nm, *r_nu; int64_t *r_off; uint8_t *r_bytes; int64_t r_n, r_cap, r_nb, r_capb; };
 const char *md_dev_last_error(void) { return t_err; }
 int md_dev_count(void) { return 1; }
@@ -56,7 +59,7 @@ int md_dev_open(int device, const md_dev_cfg *cfg, md_dev **out) {
 static void calls_drop(md_dev *h) { int i; for(i = 0; i < h->n_cch; i++) free(h->cch[i].row); free(h->cch); h->cch = NULL; h->n_cch = h->cap_cch = 0; h->calls_on = 0; }
 static void reads_drop(md_dev *h) { free(h->r_contig); free(h->r_pos); free(h->r_nm); free(h->r_nu); free(h->r_off); free(h->r_bytes); h->r_contig = h->r_pos = h->r_nm = h->r_nu = NULL; h->r_off = NULL; h->r_bytes = NULL; h->r_n = h->r_cap = h->r_nb = h->r_capb = 0; h->reads_on = 0; }
 void md_dev_close(md_dev *h) {
-    int i; if(!h) return; calls_drop(h); reads_drop(h);
+    int i; if(!h) return; calls_drop(h); reads_drop(h); free(h->mb_hist);
     for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); if(h->pr) { free(h->pr[i].kept); free(h->pr[i].cnt); } }
     free(h->pr); free(h->slot); free(h);
 }
@@ -151,6 +154,7 @@ int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     int i;
     if(!h || !cfg || (cfg->n_slots > 0 ? cfg->n_slots : 2) != h->n_slots) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reset"); return MDK_ERR_ARG; }
     calls_drop(h); reads_drop(h); memset(&h->prep, 0, sizeof(h->prep));
+    free(h->mb_hist); h->mb_hist = NULL; h->mb_len = h->mb_loaded = 0;
     for(i = 0; i < h->n_slots; i++) { sslot *s = &h->slot[i]; s->used = s->launched = s->handed_back = 0; s->ready_at = 0; if(h->pr) h->pr[i].pending = 0; }
     h->cfg = *cfg;
     return 0;
@@ -352,3 +356,82 @@ int md_reads_set_copy(const md_reads_set *r, const md_reads_cols *d, int to_host
     return 0;
 }
 void md_reads_set_free(md_reads_set *r) { if(!r) return; free(r->contig); free(r->pos); free(r->nm); free(r->nu); free(r->off); free(r->bytes); free(r); }
+
+/* ---- mbias: the histogram is the oracle's table for this run; the rows and the dense counts of csrc/mdk_bias.hip, in host memory ---- */
+static int g_mb_run;                  /* mbias runs of the process that have submitted a chunk */
+static int mbias_given(md_dev *h) {
+    static const char *AB[4] = {"OT", "OB", "CTOT", "CTOB"};
+    const char *dir = getenv("MDK_STANDIN_MBIAS"); char fn[4096], line[256]; FILE *f; int run;
+    pthread_mutex_lock(&h->mu);
+    if(h->mb_loaded) { pthread_mutex_unlock(&h->mu); return 0; }
+    h->mb_loaded = 1; run = g_mb_run++;
+    pthread_mutex_unlock(&h->mu);
+    if(!dir) { snprintf(t_err, sizeof t_err, "dev_standin: MDK_STANDIN_MBIAS is not set"); return MDK_ERR_ARG; }
+    snprintf(fn, sizeof fn, "%s/%d.txt", dir, run);
+    if(!(f = fopen(fn, "r"))) { snprintf(t_err, sizeof t_err, "dev_standin: no table %.200s", fn); return MDK_ERR_ARG; }
+    while(fgets(line, sizeof line, f)) {
+        char ab[16]; int rd, pos, st; unsigned m, u;
+        if(sscanf(line, "%15s %d %d %u %u", ab, &rd, &pos, &m, &u) != 5) continue;       /* (the header line) */
+        for(st = 0; st < 4 && strcmp(ab, AB[st]); st++) ;
+        if(st == 4 || rd < 1 || rd > 2 || pos < 1) { fclose(f); snprintf(t_err, sizeof t_err, "dev_standin: bad table line %.100s", line); return MDK_ERR_ARG; }
+        if(pos > h->mb_len) { h->mb_hist = realloc(h->mb_hist, sizeof(uint32_t) * 16 * (size_t)pos); if(!h->mb_hist) abort(); memset(h->mb_hist + 16 * (size_t)h->mb_len, 0, sizeof(uint32_t) * 16 * (size_t)(pos - h->mb_len)); h->mb_len = pos; }
+        h->mb_hist[(size_t)(pos - 1) * 16 + st * 4 + 2 * (rd - 1)] += m; h->mb_hist[(size_t)(pos - 1) * 16 + st * 4 + 2 * (rd - 1) + 1] += u;
+    }
+    fclose(f);
+    return 0;
+}
+int md_dev_mbias_submit(md_dev *h, int slot, const md_read_batch *b) { int rc = md_dev_upload(h, slot, b); return rc ? rc : mbias_given(h); }
+int md_dev_mbias_group(md_dev *h, const int *slots, int n) {
+    int i;
+    if(!h || !slots || n < 1 || n > 8 || !h->prep.no_pairing) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_mbias_group"); return MDK_ERR_ARG; }
+    for(i = 0; i < n; i++) { sslot *s = slot_of(h, slots[i]); if(!s || !s->used || s->launched) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_mbias_group: slot not freshly uploaded"); return MDK_ERR_ARG; } s->launched = 1; }
+    return mbias_given(h);
+}
+int md_dev_mbias_collect(md_dev *h, const int *slots, int n, int *rc) {
+    int i;
+    if(!h || !slots || !rc || n < 1) return MDK_ERR_ARG;
+    for(i = 0; i < n; i++) {
+        sslot *s = slot_of(h, slots[i]);
+        if(!s || !s->launched) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_mbias_collect: slot not launched"); return MDK_ERR_ARG; }
+        s->launched = 0; rc[i] = 0;
+        if(s->handed_back) { s->handed_back = 0; snprintf(t_err, sizeof t_err, "dev_standin: this chunk goes back to the host preparation"); rc[i] = MDK_ERR_PREP_HOST; }
+    }
+    return 0;
+}
+int md_dev_mbias_redone(const md_dev *h) { (void)h; return 0; }
+struct md_bias_set { int64_t n; int len; int8_t *strand, *read; int32_t *pos; int64_t *nm, *nu, *dense; uint32_t *hist; };
+int md_dev_bias_finish(md_dev *h, md_bias_set **out) {
+    md_bias_set *b; int st, q, r; const int len = h ? h->mb_len : 0; const size_t cap = 8 * (size_t)len + 1;
+    if(!h || !out) return MDK_ERR_ARG;
+    if(!(b = calloc(1, sizeof(*b)))) return MDK_ERR_NOMEM;
+    b->len = len; b->strand = malloc(cap); b->read = malloc(cap); b->pos = malloc(4 * cap); b->nm = malloc(8 * cap); b->nu = malloc(8 * cap); b->dense = malloc(8 * 2 * cap); b->hist = calloc(2 * cap, 4);
+    for(q = 0; q < 16 * len; q++) { b->hist[q] = h->mb_hist[q]; b->dense[q] = (int64_t)h->mb_hist[q]; }
+    /* the order the command prints: strand, then position, then read; a row only where it has a call */
+    for(st = 0; st < 4; st++) for(q = 0; q < len; q++) for(r = 0; r < 2; r++) {
+        const uint32_t m = h->mb_hist[(size_t)q * 16 + st * 4 + 2 * r], u = h->mb_hist[(size_t)q * 16 + st * 4 + 2 * r + 1];
+        if(!m && !u) continue;
+        b->strand[b->n] = (int8_t)st; b->read[b->n] = (int8_t)(r + 1); b->pos[b->n] = q + 1; b->nm[b->n] = m; b->nu[b->n] = u; b->n++;
+    }
+    h->mb_loaded = 0;                 /* the next run's table is the next file (its histogram starts empty: md_dev_reset) */
+    *out = b;
+    return 0;
+}
+int64_t md_bias_set_count(const md_bias_set *b) { return b ? b->n : MDK_ERR_ARG; }
+int md_bias_set_len(const md_bias_set *b) { return b ? b->len : MDK_ERR_ARG; }
+int md_bias_set_redone(const md_bias_set *b) { (void)b; return 0; }
+int md_bias_set_hist(const md_bias_set *b, md_mbias *out) { if(!b || !out) return MDK_ERR_ARG; out->len = b->len; out->count = b->hist; return 0; }
+int md_bias_set_copy(const md_bias_set *b, int column, void *dst, int to_host) {
+    const size_t n = b ? (size_t)b->n : 0; (void)to_host;
+    if(!b || !dst) return MDK_ERR_ARG;
+    switch(column) {
+    case MD_BIAS_STRAND: memcpy(dst, b->strand, n); break;
+    case MD_BIAS_READ: memcpy(dst, b->read, n); break;
+    case MD_BIAS_POS: memcpy(dst, b->pos, 4 * n); break;
+    case MD_BIAS_NMETH: memcpy(dst, b->nm, 8 * n); break;
+    case MD_BIAS_NUNMETH: memcpy(dst, b->nu, 8 * n); break;
+    case MD_BIAS_COUNTS: memcpy(dst, b->dense, 8 * 16 * (size_t)b->len); break;
+    default: return MDK_ERR_ARG;
+    }
+    return 0;
+}
+void md_bias_set_free(md_bias_set *b) { if(!b) return; free(b->strand); free(b->read); free(b->pos); free(b->nm); free(b->nu); free(b->dense); free(b->hist); free(b); }
