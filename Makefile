@@ -12,7 +12,7 @@ all: $(B)/libmdk_hip.so $(B)/libmdk_extract.so $(B)/MethylDackel tools oracle
 
 # -fgpu-rdc: the sources become ONE code object; the runtime loads a code object at the first use of one of its kernels and each load
 # costs the command ~30 ms of start-up (three of them did: pileup, preparation, inflate)
-HIPSRC := methyldackel_amd/csrc/mdk_hip.hip methyldackel_amd/csrc/mdk_comm.hip methyldackel_amd/csrc/mdk_prep.hip methyldackel_amd/csrc/mdk_inflate.hip methyldackel_amd/csrc/mdk_calls.hip methyldackel_amd/csrc/mdk_reads.hip methyldackel_amd/csrc/mdk_bias.hip
+HIPSRC := methyldackel_amd/csrc/mdk_hip.hip methyldackel_amd/csrc/mdk_comm.hip methyldackel_amd/csrc/mdk_prep.hip methyldackel_amd/csrc/mdk_inflate.hip methyldackel_amd/csrc/mdk_calls.hip methyldackel_amd/csrc/mdk_reads.hip methyldackel_amd/csrc/mdk_bias.hip methyldackel_amd/csrc/mdk_cytosines.hip
 $(B)/libmdk_hip.so: $(HIPSRC) methyldackel_amd/csrc/mdk_hip_internal.hpp methyldackel_amd/csrc/mdk_overlap_rule.h methyldackel_amd/csrc/mdk_pair_rule.h methyldackel_amd/csrc/mdk_inflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h include/mdk_hip.h
 	@mkdir -p $(B)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fgpu-rdc $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ $(HIPSRC) -ldl

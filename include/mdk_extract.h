@@ -140,7 +140,8 @@ int  mdk_bind_to_device_node(int index);
  * mdk_session_extract takes the argv of extract_main (argv[0] = "extract"), parses it with the same code and returns the same codes for
  * the same errors.  Instead of bedGraph files it returns the rows those files would hold (include/mdk_hip.h "calls on the device":
  * contig, start, end, nmeth, nunmeth, context, strand).  Differences from the command:
- *   - --fraction, --counts, --logit, --methylKit and --cytosine_report are refused with MDK_RC_UNSUPPORTED (they only shape text);
+ *   - --fraction, --counts, --logit, --methylKit and --cytosine_report are refused with MDK_RC_UNSUPPORTED (the first four only shape text; the
+ *     report's rows are another table: mdk_session_cytosines, below);
  *   - -o is ignored and no output file is written; -O / -N (writing a BBM file) behave as in the command;
  *   - MDK_RANK / MDK_WORLD are ignored: one device;
  *   - the process is never left through _exit, and the HIP runtime and the device handle stay up between runs (md_dev_reset before
@@ -209,6 +210,31 @@ int64_t mdk_bias_resubmitted(const mdk_bias *b);
 int  mdk_bias_suggested(const mdk_bias *b, int strand, int bounds[4]);
 int  mdk_bias_copy(const mdk_bias *b, int column, void *dst, int to_host);
 void mdk_bias_free(mdk_bias *b);
+
+/* ---- the same session's cytosine report: every cytosine of the reference as device-resident columns ----
+ * mdk_session_cytosines takes the argv of extract_main (argv[0] = "extract") and runs it as `extract --cytosine_report`: the option is implied
+ * and accepted if given.  Instead of <prefix>.cytosine_report.txt it returns one row per line that file would hold, in the file's order (the
+ * chunks of the schedule, ascending position within a chunk) -- include/mdk_hip.h "the cytosine report on the device":
+ *   MDK_CYTOSINES_CONTIG (int32, BAM header index), MDK_CYTOSINES_POS (int32, 1-BASED: the line's column 2), MDK_CYTOSINES_STRAND (int8, +1 a C,
+ *   -1 a G), MDK_CYTOSINES_NMETH / _NUNMETH (int32), MDK_CYTOSINES_CONTEXT (uint8, 0 CG, 1 CHG, 2 CHH), MDK_CYTOSINES_TRINUCLEOTIDE (uint8, 3 per
+ *   row: the letters of column 7).
+ * The semantics are the command's, not those of mdk_session_extract's calls: -d does not apply, a site the variant filter drops is a 0 0 row,
+ * and there is a row for every cytosine (in the contexts switched on) of every chunk of the schedule (-r, -l, --chunkSize) that is not passed
+ * over -- MDK_CHUNK_NOREF and MDK_CHUNK_BED chunks give none --, covered or not, up to the contig's end.  Under -l a chunk that a BED
+ * interval touches lists all its cytosines on both strands; only the counts are restricted.  The row set therefore depends on the reference,
+ * the contexts and the schedule alone: runs over different BAM files with the same reference and options give columns that line up row for
+ * row.  Differences from the command otherwise as for mdk_session_extract (-o ignored, nothing written or printed).  --fraction, --counts,
+ * --logit and --methylKit are refused with MDK_RC_UNSUPPORTED; --mergeContext returns what the command returns for it next to
+ * --cytosine_report.  mdk_session_extract keeps refusing --cytosine_report.  Ownership and lifetimes are those of mdk_calls; mdk_cytosines_copy
+ * is synchronous (mdk_cytosines_count entries; 3 * count bytes for MDK_CYTOSINES_TRINUCLEOTIDE). */
+typedef struct mdk_cytosines mdk_cytosines;
+enum { MDK_CYTOSINES_CONTIG = 0, MDK_CYTOSINES_POS, MDK_CYTOSINES_STRAND, MDK_CYTOSINES_NMETH, MDK_CYTOSINES_NUNMETH, MDK_CYTOSINES_CONTEXT, MDK_CYTOSINES_TRINUCLEOTIDE };   /* int32 x2, int8, int32 x2, uint8, uint8 x3 */
+int  mdk_session_cytosines(mdk_session *s, int argc, char *argv[], mdk_cytosines **out);
+int64_t mdk_cytosines_count(const mdk_cytosines *c);
+int  mdk_cytosines_n_contigs(const mdk_cytosines *c);
+const char *mdk_cytosines_contig_name(const mdk_cytosines *c, int i);
+int  mdk_cytosines_copy(const mdk_cytosines *c, int column, void *dst, int to_host);
+void mdk_cytosines_free(mdk_cytosines *c);
 
 /* ---- `mergeContext` (mergeContext.c; main.c:19,53-54): text-to-text host tool, no device work ---- */
 int  mergeContext_main(int argc, char *argv[]);

@@ -431,6 +431,46 @@ int64_t md_reads_set_name_bytes(const md_reads_set *r);
 /* synchronous copies of the columns into DEVICE memory of the set's device (to_host = 0) or host memory (to_host = 1) */
 int  md_reads_set_copy(const md_reads_set *r, const md_reads_cols *dst, int to_host);
 void md_reads_set_free(md_reads_set *r);
+
+/* ---- the cytosine report on the device (a resident session: include/mdk_extract.h mdk_session_cytosines) ----
+ * What `extract --cytosine_report` prints (csrc/host/mdk_emit.c emit_format + put_blanks), kept as columns: one row for EVERY cytosine of the
+ * reference in the contexts switched on, covered or not, inside the chunks the caller names --
+ *   contig (int32) the chunk's tid; pos (int32) 1-BASED, the line's column 2; strand (int8) +1 a C, -1 a G; nmeth, nunmeth (int32), 0 where the
+ *   position has no site or its site is dropped by the variant filter (no depth test: -d does not apply to this format); context (uint8)
+ *   0 CpG, 1 CHG, 2 CHH; trinucleotide (uint8 x 3) the line's column 7: 'C' and the two following bases, for a G of the reverse complement,
+ *   each of ACGT after case folding or 'N' (anything else, and anything past a contig end).
+ * Rows come in the order of the chunks' keys and ascending position inside a chunk.  Which rows there are depends on the contig's BASES, the
+ * contexts and the chunks alone (the context codes md_dev_set_regions masked are not used): two runs over the same reference and
+ * schedule give columns that line up row for row, whatever their reads.
+ * Sequence: md_dev_cytosines_begin; for every collected group md_dev_cytosines_group in place of md_dev_download_group; md_dev_cytosines_finish.
+ * As with the calls, group launches leave their sites on the device meanwhile.  Single caller thread for these functions of a handle.
+ * Sizing: a chunk's row count is not bounded by anything the slot knows, so it is COUNTED first (k_cyto_count over the bases of the group's
+ * chunks, queued before the wait for the group and read back after it), the run's arena is reserved for exactly that many rows more, and
+ * k_cyto_fill writes them.  Ownership as for the calls: the handle keeps the arena (grown by doubling, kept until md_dev_reset /
+ * md_dev_close); md_dev_cytosines_finish returns a set that owns its device memory at its exact size until md_cytosines_set_free. */
+typedef struct {
+    int32_t min_opposite_depth;    /* --minOppositeDepth (0: no variant filter; the handle's cfg.minOppositeDepth must match) */
+    double  max_variant_frac;      /* --maxVariantFrac */
+    int32_t ctx_on[3];             /* CpG, CHG, CHH rows wanted */
+} md_cyto_cfg;
+/* one chunk of the schedule: its place in the output order, its contig (reference resident) and [beg, end); rows stop at the contig's end */
+typedef struct { uint32_t key; int32_t tid; int64_t beg, end; } md_cyto_chunk;
+typedef struct md_cytosines_set md_cytosines_set;
+/* destination of md_cytosines_set_copy: n entries each (trinucleotide: 3 n bytes); a NULL column is not copied */
+typedef struct { int32_t *contig, *pos; int8_t *strand; int32_t *nmeth, *nunmeth; uint8_t *context, *trinucleotide; } md_cytosines_cols;
+int  md_dev_cytosines_begin(md_dev *h, const md_cyto_cfg *cfg);
+/* n <= md_dev_group_max() chunks.  slots[i] >= 0: the launched slot that holds chunk i (same contig and interval) -- waited for as
+ * md_dev_download_group waits, rc[i] what md_dev_download would have returned; only rc 0 chunks get rows (one answered with MDK_ERR_PREP_HOST
+ * is prepared on the host, submitted again and passed here alone).  slots[i] < 0: a chunk of the schedule that produced no launched slot:
+ * every row of it has zero counts, rc[i] = 0.  Returns 0 when the collection itself worked. */
+int  md_dev_cytosines_group(md_dev *h, const int *slots, const md_cyto_chunk *chunks, int n, int *rc);
+/* waits for every fill, puts the chunks in key order (k_cyto_gather) and hands the rows over */
+int  md_dev_cytosines_finish(md_dev *h, md_cytosines_set **out);
+int64_t md_cytosines_set_count(const md_cytosines_set *c);
+/* synchronous copies of the columns into DEVICE memory of the set's device (to_host = 0) or host memory (to_host = 1) */
+int  md_cytosines_set_copy(const md_cytosines_set *c, const md_cytosines_cols *dst, int to_host);
+void md_cytosines_set_free(md_cytosines_set *c);
+
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
  * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram, the calls and reads state
  * are dropped, every slot's buffers are given back.  Pointers the library returned for the handle before (md_sites, md_sites_dev,

@@ -168,7 +168,8 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_perread_submit", "md_dev_perread_download", "md_dev_perread_submit_raw", "md_dev_perread_download_raw", "md_dev_read_raw",
                "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
-               "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free"]
+               "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
+               "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
@@ -177,7 +178,8 @@ EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_
                    "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node",
                    "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free",
                    "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free",
-                   "mdk_mbias_suggest", "mdk_session_mbias", "mdk_bias_count", "mdk_bias_len", "mdk_bias_resubmitted", "mdk_bias_suggested", "mdk_bias_copy", "mdk_bias_free"]
+                   "mdk_mbias_suggest", "mdk_session_mbias", "mdk_bias_count", "mdk_bias_len", "mdk_bias_resubmitted", "mdk_bias_suggested", "mdk_bias_copy", "mdk_bias_free",
+                   "mdk_session_cytosines", "mdk_cytosines_count", "mdk_cytosines_n_contigs", "mdk_cytosines_contig_name", "mdk_cytosines_copy", "mdk_cytosines_free"]
 
 _hip = None
 _ext = None
@@ -659,7 +661,9 @@ RC_UNSUPPORTED = -23
 CALL_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("context", "uint8"), ("strand", "int8"))
 READ_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("nmeth", "int32"), ("nunmeth", "int32"), ("name_offsets", "int64"), ("name_bytes", "uint8"))
 BIAS_COLUMNS = (("strand", "int8"), ("read", "int8"), ("position", "int32"), ("nmeth", "int64"), ("nunmeth", "int64"), ("counts", "int64"))
+CYTOSINE_COLUMNS = (("contig", "int32"), ("pos", "int32"), ("strand", "int8"), ("nmeth", "int32"), ("nunmeth", "int32"), ("context", "uint8"), ("trinucleotide", "uint8"))
 STRANDS = ("OT", "OB", "CTOT", "CTOB")
+CONTEXTS = ("CG", "CHG", "CHH")
 
 
 def _session_lib():
@@ -667,7 +671,7 @@ def _session_lib():
     if not getattr(L, "_session_types", False):
         L.mdk_session_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.mdk_session_close.argtypes = [C.c_void_p]
-        for command, kind, counts in (("extract", "calls", ("count",)), ("perread", "reads", ("count", "name_bytes"))):
+        for command, kind, counts in (("extract", "calls", ("count",)), ("perread", "reads", ("count", "name_bytes")), ("cytosines", "cytosines", ("count",))):
             getattr(L, f"mdk_session_{command}").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
             for f in counts:
                 getattr(L, f"mdk_{kind}_{f}").argtypes = [C.c_void_p]
@@ -790,13 +794,41 @@ class Bias(_Columns):
         return [(STRANDS[s], r, p, m, u) for s, r, p, m, u in zip(*cols)]
 
 
+class Cytosines(_Columns):
+    """The lines `extract --cytosine_report` would write, as columns: one row for EVERY cytosine of the reference in the contexts switched
+    on, covered or not, in the file's order (the chunks of the schedule, ascending position within a chunk) -- ``contig`` (int32, index into
+    ``contigs``), ``pos`` (int32, 1-based: the line's column 2), ``strand`` (int8: +1 a C, -1 a G), ``nmeth``/``nunmeth`` (int32),
+    ``context`` (uint8: 0 CG, 1 CHG, 2 CHH) and ``trinucleotide`` (uint8 [len, 3]: the ASCII letters of column 7).  Which rows there are
+    depends on the reference, the contexts and the schedule (-r, -l, --chunkSize) alone, never on the reads: the results of two BAM files
+    run against one reference with the same options line up row for row, so ``torch.stack([a.nmeth, b.nmeth])`` is a samples x cytosines
+    matrix."""
+    COLUMNS = CYTOSINE_COLUMNS
+    KIND = "cytosines"
+
+    @classmethod
+    def _sizes(cls, L, out, n):
+        return {"trinucleotide": 3 * n}
+
+    @classmethod
+    def _build(cls, L, out, cols):
+        cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
+        return super()._build(L, out, cols)
+
+    def rows(self):
+        """(chrom, pos, "+"/"-", nmeth, nunmeth, "CG"/"CHG"/"CHH", trinucleotide) tuples on the host: the seven fields of a line"""
+        cols = [getattr(self, n).cpu().tolist() for n in ("contig", "pos", "strand", "nmeth", "nunmeth", "context")]
+        tri = self.trinucleotide.cpu().numpy().tobytes().decode("latin-1")
+        return [(self.contigs[c], p, "+" if s > 0 else "-", m, u, CONTEXTS[x], tri[3 * i:3 * i + 3]) for i, (c, p, s, m, u, x) in enumerate(zip(*cols))]
+
+
 class Session:
     """One process, one device handle, many `extract` runs: ``Session(device=0).extract(args) -> Calls``.  ``args`` is the extract
     command line as for run_cli (without the command name).  The rows never pass through text: they are compacted on the device
     (k_calls_compact) and copied device to device into tensors torch allocated on ``torch.device("cuda", device)``; with
     ``device_tensors=False`` into CPU tensors instead.  --fraction/--counts/--logit/--methylKit/--cytosine_report are refused (rc -23),
     -o is ignored; any non-zero return code raises MdkError with ``.rc``.  ``perread(args) -> Reads`` runs `perRead` command lines on the
-    same handle."""
+    same handle, ``mbias(args) -> Bias`` `mbias` ones, and ``cytosine_report(args) -> Cytosines`` gives the one output of `extract` that
+    ``extract`` refuses: a row for every cytosine of the reference."""
 
     def __init__(self, device: int = 0):
         self.device = device
@@ -807,7 +839,7 @@ class Session:
             raise _rc_error("mdk_session_open", rc)
         self._h = h
 
-    def _run(self, command, result, args, device_tensors):
+    def _run(self, command, result, args, device_tensors, entry=None):
         """one run of `command` on the handle: its mdk_<kind> object copied, column by column, into tensors -- device to device into
         tensors torch allocated on the session's device, or into CPU tensors -- and freed"""
         import torch
@@ -817,9 +849,9 @@ class Session:
         argv = [command] + [str(a) for a in args]
         arr = (C.c_char_p * (len(argv) + 1))(*[os.fsencode(a) for a in argv], None)
         out = C.c_void_p()
-        rc = getattr(L, f"mdk_session_{command.lower()}")(self._h, len(argv), arr, C.byref(out))
+        rc = getattr(L, f"mdk_session_{entry or command.lower()}")(self._h, len(argv), arr, C.byref(out))
         if rc:
-            raise _rc_error(command, rc)
+            raise _rc_error(entry or command, rc)
         try:
             n = int(getattr(L, f"mdk_{kind}_count")(out))
             size = result._sizes(L, out, n)                     # every other column: n
@@ -850,6 +882,14 @@ class Session:
         bounds, as Bias.  Parsed as the command parses it (without --noSVG the output prefix is still required), but the prefix is ignored:
         no SVG is written and nothing is printed.  ``s.extract(args + b.options())`` is the run the suggestion is for."""
         return self._run("mbias", Bias, args, device_tensors)
+
+    def cytosine_report(self, args, device_tensors: bool = True) -> Cytosines:
+        """The `extract` command line (without the command name) run as `extract --cytosine_report` on the same handle: the rows of
+        <prefix>.cytosine_report.txt as Cytosines.  --cytosine_report is implied (and accepted if given), -o is ignored, nothing is written
+        or printed.  The command's semantics, not those of ``extract``'s Calls: -d does not apply, a site the variant filter drops is a
+        0 0 row, uncovered cytosines are rows.  --fraction/--counts/--logit/--methylKit are refused (rc -23); --mergeContext returns what
+        the command returns for it."""
+        return self._run("extract", Cytosines, args, device_tensors, entry="cytosines")
 
     def close(self):
         if self._h is not None:

@@ -84,8 +84,9 @@ MDK_LOCAL void *devopen_main(void *arg) { devopen_t *d = arg; d->rc = md_dev_ope
 static int g_ngroups = 3;            /* groups in flight (MDK_GROUPS_IN_FLIGHT=n, 2..6) */
 #define MDK_NGROUPS g_ngroups
 enum { G_FREE = 0, G_FILL, G_LAUNCHED };
-enum { SINK_TEXT = 0, SINK_CALLS, SINK_BIAS };      /* where collected groups go: the text emitter (extract_main); the device calls of a session (md_dev_calls_group); the mbias
-                                                     * histogram of a session -- nothing comes back per chunk, the collector reads the group's status blocks (md_dev_mbias_collect) */
+enum { SINK_TEXT = 0, SINK_CALLS, SINK_BIAS, SINK_CYTO };      /* where collected groups go: the text emitter (extract_main); the device calls of a session (md_dev_calls_group); the mbias
+                                                     * histogram of a session -- nothing comes back per chunk, the collector reads the group's status blocks (md_dev_mbias_collect); the
+                                                     * cytosine report of a session (md_dev_cytosines_group): every chunk that is not skipped has rows, with or without reads */
 typedef struct { mdk_chunk ch[MDK_GROUP]; int slot[MDK_GROUP]; int n, launched[MDK_GROUP], inplace[MDK_GROUP], single[MDK_GROUP], state, held, n_held, rel_slot[MDK_GROUP]; mdk_chunk rel_ch[MDK_GROUP]; } cgroup;      /* held: the host memory behind its records has not been given back yet; inplace: the device reads the chunk's records where the piece they were inflated in holds them (md_dev_upload_raw_inplace): that piece goes back when the chunk's results are in */
 typedef struct {
     mdk_plan *p; md_dev *dev; emitter *em; cgroup G[MDK_NGROUPS_MAX];
@@ -111,6 +112,7 @@ static void release_uploaded(xpipe *X, int block) {
         g->held = 0; block = 0;
     }
 }
+static md_cyto_chunk cyto_chunk(const mdk_chunk *c) { md_cyto_chunk q; q.key = c->index; q.tid = c->tid; q.beg = c->beg; q.end = c->end; return q; }
 static void xp_fail(xpipe *X, int ret) { pthread_mutex_lock(&X->mu); if(!X->ret) X->ret = ret; pthread_cond_broadcast(&X->cv); pthread_mutex_unlock(&X->mu); }
 
 /* the contigs' bases (and BED runs, mappability tracks) go to the device ahead of the chunks, in schedule order */
@@ -177,6 +179,14 @@ static void *collector_main(void *arg) {
         case SINK_CALLS:
             if(nl) { uint32_t keys[MDK_GROUP]; for(i = 0; i < nl; i++) keys[i] = g->ch[li[i]].index; rc = md_dev_calls_group(dev, ls, keys, nl, rcs); }
             break;
+        case SINK_CYTO: {    /* the launched chunks first (rcs[i] belongs to li[i]), then any chunk of the schedule that was not skipped and not launched: its rows are all 0 0 */
+            int cs[MDK_GROUP], crc[MDK_GROUP], nc = nl; md_cyto_chunk cq[MDK_GROUP];
+            memset(crc, 0, sizeof(crc));
+            for(i = 0; i < nl; i++) { cs[i] = ls[i]; cq[i] = cyto_chunk(&g->ch[li[i]]); }
+            for(i = 0; i < g->n && !rc; i++) if(!g->launched[i] && !g->ch[i].skipped) { rc = ref_wait(X, g->ch[i].tid); cs[nc] = -1; cq[nc] = cyto_chunk(&g->ch[i]); nc++; }
+            if(nc && !rc) rc = md_dev_cytosines_group(dev, cs, cq, nc, crc);
+            for(i = 0; i < nl; i++) rcs[i] = crc[i];
+            break; }
         default:
             if(nl) rc = md_dev_download_group(dev, ls, nl, st, rcs);
         }
@@ -192,6 +202,7 @@ static void *collector_main(void *arg) {
                 if(!rc) rc = X->sink == SINK_BIAS ? md_dev_mbias_submit(dev, g->slot[k], &g->ch[k].batch) : md_dev_submit(dev, g->slot[k], &g->ch[k].batch);
                 if(!rc && X->sink == SINK_BIAS) rc = md_dev_slot_sync(dev, g->slot[k]);
                 else if(!rc && X->sink == SINK_CALLS) { int rc1 = 0; rc = md_dev_calls_group(dev, &g->slot[k], &g->ch[k].index, 1, &rc1); if(!rc) rc = rc1; }
+                else if(!rc && X->sink == SINK_CYTO) { int rc1 = 0; const md_cyto_chunk q = cyto_chunk(&g->ch[k]); rc = md_dev_cytosines_group(dev, &g->slot[k], &q, 1, &rc1); if(!rc) rc = rc1; }
                 else if(!rc) rc = md_dev_download(dev, g->slot[k], &st[i]);
                 X->n_host_prep++;
             }
@@ -241,6 +252,20 @@ static void session_options(mdk_plan *p, void *arg) {
     mdk_plan_dev_cfg(p, &o->d.cfg);
     session_geometry(&o->d.cfg);
 }
+/* the same for mdk_session_cytosines: --cytosine_report is what the run is (implied, accepted if given), the formats that are arithmetic on
+ * columns are refused as above, and --mergeContext ends as it ends the command.  The device is configured as the command configures it */
+static void session_options_cyto(mdk_plan *p, void *arg) {
+    xopen *o = arg; opts_t *q = &p->o;
+    p->no_text = 1;
+    if(q->fraction || q->counts || q->logit || q->methylkit) {
+        fprintf(stderr, "[mdk] --fraction, --counts, --logit and --methylKit only shape text output: a session returns the report's rows themselves\n");
+        p->open_rc = MDK_RC_UNSUPPORTED; return;
+    }
+    if(q->merge) { fprintf(stderr, "--mergeContext and --cytosine_report are mutually exclusive.\n"); plan_usage(); p->open_rc = 1; return; }
+    q->cytosine_report = 1;
+    mdk_plan_dev_cfg(p, &o->d.cfg);
+    session_geometry(&o->d.cfg);
+}
 MDK_LOCAL void session_geometry(md_dev_cfg *cfg) {
     if(getenv("MDK_GROUPS_IN_FLIGHT")) { g_ngroups = atoi(getenv("MDK_GROUPS_IN_FLIGHT")); if(g_ngroups < 2) g_ngroups = 2; if(g_ngroups > MDK_NGROUPS_MAX) g_ngroups = MDK_NGROUPS_MAX; }
     else g_ngroups = 3;
@@ -249,15 +274,18 @@ MDK_LOCAL void session_geometry(md_dev_cfg *cfg) {
 
 /* extract_main's pipeline; S != NULL: a session's run -- no output files, no emitter, every collected group compacted into calls on S's device
  * handle (opened at the first run, reset before every later one), handed over in *out.  mbias (a session's only): the command line is mbias_main's, the
- * groups are launched with md_dev_mbias_group and leave nothing but their status blocks, and the run ends with the histogram's table (md_dev_bias_finish) */
-static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int mbias) {
+ * groups are launched with md_dev_mbias_group and leave nothing but their status blocks, and the run ends with the histogram's table (md_dev_bias_finish).
+ * RUN_CYTO (a session's only): the extract command line with --cytosine_report implied; the collected groups become the report's rows (md_dev_cytosines_group) */
+enum { RUN_EXTRACT = 0, RUN_MBIAS, RUN_CYTO };
+static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int mode) {
+    const int mbias = mode == RUN_MBIAS, cyto = mode == RUN_CYTO;
     mdk_plan *p = NULL; md_dev *dev = NULL; xpipe *X = NULL; int rc, ret = 0, more = 1, i, g_i; xopen dop; pthread_t cth, rth, preg; int cth_ok = 0, rth_ok = 0, preg_ok = 0; emitter em;
     double T0 = now_s(), t_open, t_dev, w_next = 0, w_sub = 0, w_group = 0, w_ref = 0, w_rel = 0, ta; uint64_t n_chunks = 0; int32_t ref_t0, ref_t1;
     if(getenv("MDK_HOST_PROFILE")) { struct timespec ts; clock_gettime(CLOCK_REALTIME, &ts); fprintf(stderr, "[mdk main] entered at epoch %.3f\n", ts.tv_sec + 1e-9 * ts.tv_nsec); }
     if(argc > 2 && !S) hip_warm_up();
     memset(&dop, 0, sizeof(dop)); memset(&em, 0, sizeof(em));
     if(mbias) { rc = mdk_plan_open_mbias(argc, argv, &p); if(!rc && p) { mdk_plan_dev_cfg(p, &dop.d.cfg); session_geometry(&dop.d.cfg); } }
-    else rc = plan_open_ex(argc, argv, &p, S ? session_options : xopen_start, &dop);
+    else rc = plan_open_ex(argc, argv, &p, S ? (cyto ? session_options_cyto : session_options) : xopen_start, &dop);
     t_open = now_s() - T0;
     if(rc != 0 || !p) { if(dop.started) { pthread_join(dop.th, NULL); if(dop.d.dev) md_dev_close(dop.d.dev); } return rc; }
     if(getenv("MDK_HOST_PROFILE")) fprintf(stderr, "[mdk main] resident after plan open %.0f MB\n", rss_mb(0));
@@ -279,6 +307,13 @@ static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int 
     X = calloc(1, sizeof(*X));
     if(X) X->ref_state = calloc((size_t)p->bam->n_targets + 1, sizeof(int));
     if(X && mbias) X->sink = SINK_BIAS;
+    else if(X && cyto) {       /* the report's sink: the variant filter and the contexts of the text post-pass, no depth test */
+        md_cyto_cfg yc; memset(&yc, 0, sizeof(yc));
+        yc.min_opposite_depth = p->o.min_opp_depth > 0 ? p->o.min_opp_depth : 0; yc.max_variant_frac = p->o.max_variant_frac;
+        for(i = 0; i < 3; i++) yc.ctx_on[i] = p->o.ctx_on[i];
+        X->sink = SINK_CYTO;
+        if(md_dev_cytosines_begin(dev, &yc)) { fprintf(stderr, "[mdk] device error: %s\n", md_dev_last_error()); free(X->ref_state); free(X); mdk_plan_detach_device(p); mdk_plan_close(p); return MDK_RC_DEVICE; }
+    }
     else if(X && S) {     /* the session's sink: the calls configuration is the text post-pass's */
         md_calls_cfg cc; memset(&cc, 0, sizeof(cc));
         cc.min_depth = p->o.min_depth; cc.merge = p->o.merge; cc.min_opposite_depth = p->o.min_opp_depth > 0 ? p->o.min_opp_depth : 0; cc.max_variant_frac = p->o.max_variant_frac;
@@ -374,6 +409,10 @@ static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int 
         ret = session_result(ret, frc, p, sizeof(mdk_bias), set, set ? md_bias_set_count(set) : 0, out);
         if(ret) md_bias_set_free(set);
         else { mdk_bias *b = *out; md_mbias hist; b->len = md_bias_set_len(set); b->redone = md_bias_set_redone(set); if(md_bias_set_hist(set, &hist) || mdk_mbias_suggest(&hist, b->bounds, b->has)) { mdk_bias_free(b); *out = NULL; ret = MDK_RC_DEVICE; } }
+    } else if(cyto) {       /* the report's rows, in schedule order; the handle's state is finished either way */
+        md_cytosines_set *set = NULL; const int frc = md_dev_cytosines_finish(dev, &set);
+        ret = session_result(ret, frc, p, sizeof(mdk_cytosines), set, md_cytosines_set_count(set), out);
+        if(ret) md_cytosines_set_free(set);
     } else if(S) {          /* the rows, in schedule order, handed over with the contig names; the handle's calls state is finished either way */
         md_calls_set *set = NULL; const int frc = md_dev_calls_finish(dev, &set);
         ret = session_result(ret, frc, p, sizeof(mdk_calls), set, md_calls_set_count(set), out);
@@ -391,8 +430,9 @@ static int pipeline_run(int argc, char *argv[], mdk_session *S, void **out, int 
     return ret;
 }
 
-static int extract_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, 0); }
-MDK_LOCAL int session_mbias_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, 1); }
+static int extract_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, RUN_EXTRACT); }
+MDK_LOCAL int session_mbias_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, RUN_MBIAS); }
+static int cytosines_run(int argc, char *argv[], mdk_session *S, void **out) { return pipeline_run(argc, argv, S, out, RUN_CYTO); }
 
 int extract_main(int argc, char *argv[]) {
     { int rk = 0, wd = 1, m = ranks_from_env(&rk, &wd); if(m < 0) return -1; if(m > 0) return extract_ranks(argc, argv, rk, wd); }       /* one process per GPU (mdk_ranks.c) */
@@ -419,3 +459,24 @@ int mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host) {
     return md_calls_set_copy(c->r.set, &d, to_host);
 }
 void mdk_calls_free(mdk_calls *c) { if(c) { md_calls_set_free(c->r.set); session_result_free(&c->r); } }
+
+int mdk_session_cytosines(mdk_session *s, int argc, char *argv[], mdk_cytosines **out) { return session_run(s, argc, argv, (void **)out, sizeof(mdk_cytosines), cytosines_run); }
+int64_t mdk_cytosines_count(const mdk_cytosines *c) { return c ? c->r.n : -1; }
+int mdk_cytosines_n_contigs(const mdk_cytosines *c) { return result_n_contigs(c ? &c->r : NULL); }
+const char *mdk_cytosines_contig_name(const mdk_cytosines *c, int i) { return result_contig_name(c ? &c->r : NULL, i); }
+int mdk_cytosines_copy(const mdk_cytosines *c, int column, void *dst, int to_host) {
+    md_cytosines_cols d; memset(&d, 0, sizeof(d));
+    if(!c || !dst || column < 0 || column > MDK_CYTOSINES_TRINUCLEOTIDE) return MDK_ERR_ARG;
+    if(!c->r.set || c->r.n == 0) return 0;
+    switch(column) {
+    case MDK_CYTOSINES_CONTIG: d.contig = dst; break;
+    case MDK_CYTOSINES_POS: d.pos = dst; break;
+    case MDK_CYTOSINES_STRAND: d.strand = dst; break;
+    case MDK_CYTOSINES_NMETH: d.nmeth = dst; break;
+    case MDK_CYTOSINES_NUNMETH: d.nunmeth = dst; break;
+    case MDK_CYTOSINES_CONTEXT: d.context = dst; break;
+    default: d.trinucleotide = dst; break;
+    }
+    return md_cytosines_set_copy(c->r.set, &d, to_host);
+}
+void mdk_cytosines_free(mdk_cytosines *c) { if(c) { md_cytosines_set_free(c->r.set); session_result_free(&c->r); } }

@@ -17,6 +17,7 @@ static void usage(void) {
 " -M/--mappability FILE, -O, -N FILE, -l FILE, --keepStrand, --version\n"
 "\nNote that --fraction, --counts, and --logit are mutually exclusive!\n", stderr);
 }
+MDK_LOCAL void plan_usage(void) { usage(); }
 
 /* 4 comma-separated non-negative ints (the reference's parseBounds, common.c:11-43) */
 MDK_LOCAL void parse_bounds(const char *arg, int *dst) {

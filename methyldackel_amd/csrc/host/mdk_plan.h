@@ -147,6 +147,7 @@ typedef struct { void *set; int64_t n; int n_contigs; char **names; } mdk_result
 struct mdk_calls { mdk_result r; };
 struct mdk_reads { mdk_result r; int64_t n_bytes; };
 struct mdk_bias { mdk_result r; int len, redone, bounds[16], has[4]; };
+struct mdk_cytosines { mdk_result r; };
 MDK_LOCAL int session_mbias_run(int argc, char *argv[], mdk_session *S, void **out);      /* (mdk_extract.c) extract_run's pipeline with the histogram as its sink */
 typedef int (*session_run_fn)(int argc, char *argv[], mdk_session *S, void **out);
 MDK_LOCAL int session_run(mdk_session *s, int argc, char *argv[], void **out, size_t size, session_run_fn run);     /* mdk_session_<command>: argument check, the run, an empty result of `size` bytes where it made none */
@@ -158,6 +159,7 @@ MDK_LOCAL int result_n_contigs(const mdk_result *r);
 MDK_LOCAL const char *result_contig_name(const mdk_result *r, int i);
 
 MDK_LOCAL void plan_free(mdk_plan *p);
+MDK_LOCAL void plan_usage(void);              /* extract's usage text, as a refused command line prints it */
 MDK_LOCAL int plan_open_ex(int argc, char *argv[], mdk_plan **out, void (*after_options)(mdk_plan *, void *), void *ctx);
 MDK_LOCAL int plan_attach_inputs(mdk_plan *p, char *argv[], int first_positional);
 MDK_LOCAL void parse_bounds(const char *arg, int *dst);

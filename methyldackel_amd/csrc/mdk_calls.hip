@@ -56,10 +56,8 @@ __device__ __forceinline__ bool calls_nbr(const KCallsSlot &S, int t, int i, int
     }
     return false;
 }
-// the variant filter of extract.c:444-459 (the ratio in double, as the host computes it)
-__device__ __forceinline__ bool calls_variant(const KCalls &K, bool has_var, const md_site_var &v) {
-    return has_var && K.min_opp > 0 && v.noff >= (uint32_t)K.min_opp && (double)v.nvar / (double)v.noff >= K.max_vf;
-}
+// the variant filter (site_is_variant, mdk_hip_internal.hpp) with this launch's thresholds
+__device__ __forceinline__ bool calls_variant(const KCalls &K, bool has_var, const md_site_var &v) { return site_is_variant(K.min_opp, K.max_vf, has_var, v); }
 
 __global__ __launch_bounds__(CALLS_WG) void k_calls_compact(const KCalls K) {
     const int b = blockIdx.x;

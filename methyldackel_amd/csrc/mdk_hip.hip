@@ -1126,7 +1126,7 @@ extern "C" void md_dev_close(md_dev *h) {
     if(h->piece_inf) (void)hipStreamDestroy(h->piece_inf);
     if(h->ref_stream) (void)hipStreamDestroy(h->ref_stream);
     g_open_handles.fetch_sub(1);                       // (before the last carved buffers go: the give that brings the count to zero may start the blocks over)
-    calls_state_free(h); reads_state_free(h);
+    calls_state_free(h); reads_state_free(h); cyto_state_free(h);
     h->d_status.release(); h->h_status.release();
     if(h->d_crc) (void)hipFree(h->d_crc);
     if(h->d_hist) (void)hipFree(h->d_hist);
@@ -1161,6 +1161,7 @@ extern "C" int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     if(h->calls) { calls_state_free(h); }
     h->no_pack = false;
     reads_state_free(h); h->reads_on = false;
+    cyto_state_free(h);
     for(Slot &s : h->slots) {
         slot_buffers_release(s);
         Slot f;                           // the slot as md_dev_open made it: its stream, events and status block stay

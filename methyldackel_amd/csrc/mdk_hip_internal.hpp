@@ -132,10 +132,13 @@ struct CallsState;                          // mdk_calls.hip
 MDK_HIDDEN void calls_state_free(md_dev *h);
 struct ReadsState;                          // mdk_reads.hip
 MDK_HIDDEN void reads_state_free(md_dev *h);
+struct CytoState;                           // mdk_cytosines.hip
+MDK_HIDDEN void cyto_state_free(md_dev *h);
 struct md_dev {
     int device; md_dev_cfg cfg; int tile, n_slots; bool variant; bool qw = false;
     CallsState *calls = nullptr; bool no_pack = false;     // md_dev_calls_*: the compaction's state; no_pack: group launches leave their sites on the device
     ReadsState *reads = nullptr; bool reads_on = false;    // md_dev_reads_*: the perRead rows' state; reads_on: md_dev_perread_submit_raw copies nothing back
+    CytoState *cyto = nullptr;                             // md_dev_cytosines_*: the cytosine report's state
     std::vector<hipStream_t> streams;        // the streams the slots work on (cfg.n_streams of them, or one per slot)
     std::mutex crc_mu; void *d_crc = nullptr;   // constants of k_crc32 (mdk_inflate.hip), made by the first piece
     std::mutex piece_mu; std::vector<hipStream_t> piece_streams; int piece_rr = 0; hipStream_t piece_in = nullptr, piece_inf = nullptr;      /* the pieces' lanes (mdk_inflate.hip): the stream their compressed bytes cross the link on, the stream k_inflate runs on */      // the pieces' streams: a few, shared (mdk_inflate.hip piece_stream_of)
@@ -192,6 +195,11 @@ __device__ __forceinline__ md_pr_count perread_walk(const uint8_t *seq, const ui
     return o;
 }
 
+// the variant filter of extract.c:444-459 (the ratio in double, as the host computes it): what the calls and the cytosine report drop
+__device__ __forceinline__ bool site_is_variant(int32_t min_opp, double max_vf, bool has_var, const md_site_var &v) {
+    return has_var && min_opp > 0 && v.noff >= (uint32_t)min_opp && (double)v.nvar / (double)v.noff >= max_vf;
+}
+
 // MDK_HOST_PROFILE=1: where the host threads' time inside the library goes (seconds and calls per site), printed by md_dev_profile_dump
 enum { PF_UP_SYNC = 0, PF_UP_ALLOC, PF_UP_COPY, PF_LAUNCH, PF_FIN_WAIT, PF_DL_COPY, PF_DL_ORDER, PF_SETREF, PF_PIECE_SUBMIT, PF_PIECE_WAIT, PF_GRP_DEV, PF_GRP_TURN, PF_N };
 MDK_HIDDEN bool mdk_prof_on();
@@ -222,6 +230,7 @@ struct ColSpec { uint32_t elem, extra; };        // bytes per entry; entries the
 #define CALLS_TILES_FLOOR (1u << 14)             // entries of the calls' tile table
 #define READS_ROWS_FLOOR (1u << 18)              // rows of the reads' run arena
 #define READS_BYTES_FLOOR (1u << 22)             // name bytes of the reads' run arena
+#define CYTO_ROWS_FLOOR (1u << 20)               // rows of the cytosine report's run arena
 struct ColTable {
     const ColSpec *spec; int k; const char *what;           // `what` names the table in the allocation's error message
     char *mem = nullptr; uint64_t cap = 0; size_t at[COLTAB_MAXK] = {};

@@ -11,6 +11,8 @@
  * oracle's `perRead` lines for the same command line, in order (MDK_STANDIN_PERREAD); md_dev_reads_* keep the rows in host memory.
  * mbias (tests/test_bias_cpu.py): the stand-in cannot count, so the histogram of the process's i-th mbias run is GIVEN -- the oracle's --noSVG
  * table, $MDK_STANDIN_MBIAS/<i>.txt, added when the run's first chunk is submitted; md_dev_bias_finish restates k_bias_rows' order rule.
+ * cytosine report (tests/test_cytosines_cpu.py): md_dev_set_reference keeps a copy of each contig, and md_dev_cytosines_* restate the rules of
+ * csrc/mdk_cytosines.hip over those bases and the slot's sites.
  *   build: gcc -O2 -shared -fPIC -Iinclude -o tools/_build/libmdk_dev_standin.so tools/dev_standin.c -lz -lpthread */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -35,11 +37,15 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 typedef struct { double ready_at; int used, launched, handed_back; int32_t tid; int64_t beg, end; uint8_t *raw; uint64_t raw_bytes, raw_cap; uint32_t *off; uint32_t n_rec, off_cap; md_site *site; md_site_var *var; int64_t cap; } sslot;
 typedef struct { int32_t start, end, nm, nu; uint8_t ctx; int8_t strand; } crow_t;
 typedef struct { uint32_t key; int32_t tid; crow_t *row; int64_t n; } cchunk_t;
+typedef struct { int32_t pos, nm, nu; int8_t strand; uint8_t ctx, tri[3]; } yrow_t;
+struct ychunk { uint32_t key; int32_t tid; yrow_t *row; int64_t n; };
 typedef struct { uint32_t *kept; md_pr_count *cnt; int64_t n, cap; int pending; } prslot_t;       /* perRead: the kept reads of a slot's chunk and their counts */
 struct md_dev { md_dev_cfg cfg; int n_slots; sslot *slot; long n_up; int handback; pthread_mutex_t mu; double busy_until; int us_per_krec;
                 md_calls_cfg ccfg; int calls_on; cchunk_t *cch; int n_cch, cap_cch;
                 md_prep_cfg prep; prslot_t *pr; int64_t pr_next;           /* pr_next: the oracle's perRead line the next kept read must match */
                 uint32_t *mb_hist; int mb_len, mb_loaded;                  /* mbias: the given histogram [q][16], its rows, whether this run's table is in */
+                char **ref; int64_t *reflen; int n_ref;                   /* the contigs' bases (md_dev_set_reference), for the cytosine report */
+                md_cyto_cfg ycfg; int cyto_on; struct ychunk *ych; int n_ych, cap_ych;
                 int reads_on; int32_t *r_contig, *r_pos, *r_nm, *r_nu; int64_t *r_off; uint8_t *r_bytes; int64_t r_n, r_cap, r_nb, r_capb; };
 const char *md_dev_last_error(void) { return t_err; }
 int md_dev_count(void) { return 1; }
@@ -58,14 +64,30 @@ int md_dev_open(int device, const md_dev_cfg *cfg, md_dev **out) {
 }
 static void calls_drop(md_dev *h) { int i; for(i = 0; i < h->n_cch; i++) free(h->cch[i].row); free(h->cch); h->cch = NULL; h->n_cch = h->cap_cch = 0; h->calls_on = 0; }
 static void reads_drop(md_dev *h) { free(h->r_contig); free(h->r_pos); free(h->r_nm); free(h->r_nu); free(h->r_off); free(h->r_bytes); h->r_contig = h->r_pos = h->r_nm = h->r_nu = NULL; h->r_off = NULL; h->r_bytes = NULL; h->r_n = h->r_cap = h->r_nb = h->r_capb = 0; h->reads_on = 0; }
+static void cyto_drop(md_dev *h) { int i; for(i = 0; i < h->n_ych; i++) free(h->ych[i].row); free(h->ych); h->ych = NULL; h->n_ych = h->cap_ych = 0; h->cyto_on = 0; }
+static void refs_drop(md_dev *h) { int i; for(i = 0; i < h->n_ref; i++) free(h->ref[i]); free(h->ref); free(h->reflen); h->ref = NULL; h->reflen = NULL; h->n_ref = 0; }
 void md_dev_close(md_dev *h) {
-    int i; if(!h) return; calls_drop(h); reads_drop(h); free(h->mb_hist);
+    int i; if(!h) return; calls_drop(h); reads_drop(h); cyto_drop(h); refs_drop(h); free(h->mb_hist);
     for(i = 0; i < h->n_slots; i++) { free(h->slot[i].raw); free(h->slot[i].off); free(h->slot[i].site); free(h->slot[i].var); if(h->pr) { free(h->pr[i].kept); free(h->pr[i].cnt); } }
     free(h->pr); free(h->slot); free(h);
 }
 int md_dev_tile(const md_dev *h) { (void)h; return 2048; }
 int md_dev_reserve_contigs(md_dev *h, int32_t n) { (void)h; (void)n; return 0; }
-int md_dev_set_reference(md_dev *h, int32_t tid, const char *seq, int64_t len) { (void)h; (void)tid; (void)seq; (void)len; return 0; }
+int md_dev_set_reference(md_dev *h, int32_t tid, const char *seq, int64_t len) {      /* (a thread of its own calls this, next to the collector) */
+    char *copy;
+    if(!h || tid < 0 || !seq || len < 0) return MDK_ERR_ARG;
+    if(!(copy = malloc((size_t)len + 1))) return MDK_ERR_NOMEM;
+    memcpy(copy, seq, (size_t)len);
+    pthread_mutex_lock(&h->mu);
+    if(tid >= h->n_ref) {
+        h->ref = realloc(h->ref, sizeof(char *) * (size_t)(tid + 1)); h->reflen = realloc(h->reflen, sizeof(int64_t) * (size_t)(tid + 1));
+        if(!h->ref || !h->reflen) abort();
+        while(h->n_ref <= tid) { h->ref[h->n_ref] = NULL; h->reflen[h->n_ref] = 0; h->n_ref++; }
+    }
+    free(h->ref[tid]); h->ref[tid] = copy; h->reflen[tid] = len;
+    pthread_mutex_unlock(&h->mu);
+    return 0;
+}
 int md_dev_set_regions(md_dev *h, int32_t tid, const md_region *runs, int64_t n) { (void)h; (void)tid; (void)runs; (void)n; return 0; }
 int md_dev_set_mappability(md_dev *h, int32_t tid, const uint32_t *bits, int64_t n) { (void)h; (void)tid; (void)bits; (void)n; return 0; }
 int md_dev_set_prep(md_dev *h, const md_prep_cfg *cfg) { if(h && cfg) h->prep = *cfg; return 0; }
@@ -153,7 +175,7 @@ struct md_calls_set { int64_t n; int32_t *contig, *start, *end, *nm, *nu; uint8_
 int md_dev_reset(md_dev *h, const md_dev_cfg *cfg) {
     int i;
     if(!h || !cfg || (cfg->n_slots > 0 ? cfg->n_slots : 2) != h->n_slots) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_reset"); return MDK_ERR_ARG; }
-    calls_drop(h); reads_drop(h); memset(&h->prep, 0, sizeof(h->prep));
+    calls_drop(h); reads_drop(h); cyto_drop(h); refs_drop(h); memset(&h->prep, 0, sizeof(h->prep));
     free(h->mb_hist); h->mb_hist = NULL; h->mb_len = h->mb_loaded = 0;
     for(i = 0; i < h->n_slots; i++) { sslot *s = &h->slot[i]; s->used = s->launched = s->handed_back = 0; s->ready_at = 0; if(h->pr) h->pr[i].pending = 0; }
     h->cfg = *cfg;
@@ -245,6 +267,90 @@ int md_calls_set_copy(const md_calls_set *c, const md_calls_cols *d, int to_host
     return 0;
 }
 void md_calls_set_free(md_calls_set *c) { if(!c) return; free(c->contig); free(c->start); free(c->end); free(c->nm); free(c->nu); free(c->ctx); free(c->strand); free(c); }
+
+/* ---- the cytosine report on the "device": the rows k_cyto_fill makes (csrc/mdk_cytosines.hip), restated over the contig's bases and the slot's sites ---- */
+struct md_cytosines_set { int64_t n; int32_t *contig, *pos, *nm, *nu; int8_t *strand; uint8_t *ctx, *tri; };
+static int y_at(const char *seq, int64_t len, int64_t i) { return (i >= 0 && i < len) ? (unsigned char)seq[i] : 0; }      /* past either end: no base */
+static int y_code(const char *seq, int64_t len, int64_t i) {       /* k_classify's code: 0, or 1 + 2 * type + isG */
+    const int c = y_at(seq, len, i) & 0x5f;
+    if(c == 'C') return (y_at(seq, len, i + 1) & 0x5f) == 'G' ? 1 : (y_at(seq, len, i + 2) & 0x5f) == 'G' ? 3 : 5;
+    if(c == 'G') return (y_at(seq, len, i - 1) & 0x5f) == 'C' ? 2 : (y_at(seq, len, i - 2) & 0x5f) == 'C' ? 4 : 6;
+    return 0;
+}
+static uint8_t y_fwd(int b) { b &= 0x5f; return (b == 'A' || b == 'C' || b == 'G' || b == 'T') ? (uint8_t)b : (uint8_t)'N'; }
+static uint8_t y_comp(int b) { switch(b) { case 'A': case 'a': return 'T'; case 'C': case 'c': return 'G'; case 'G': case 'g': return 'C'; case 'T': case 't': return 'A'; default: return 'N'; } }
+int md_dev_cytosines_begin(md_dev *h, const md_cyto_cfg *cfg) {
+    if(!h || !cfg || (!cfg->ctx_on[0] && !cfg->ctx_on[1] && !cfg->ctx_on[2])) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_cytosines_begin"); return MDK_ERR_ARG; }
+    cyto_drop(h); h->ycfg = *cfg; h->cyto_on = 1;
+    return 0;
+}
+int md_dev_cytosines_group(md_dev *h, const int *slots, const md_cyto_chunk *chunks, int n, int *rc) {
+    int i;
+    if(!h || !slots || !chunks || !rc || n < 1 || n > 8 || !h->cyto_on) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_cytosines_group"); return MDK_ERR_ARG; }
+    for(i = 0; i < n; i++) {
+        const md_cyto_chunk *q = &chunks[i]; md_sites st; struct ychunk c; const char *seq; int64_t len, p, k = 0, end;
+        memset(&st, 0, sizeof(st)); rc[i] = 0;
+        pthread_mutex_lock(&h->mu);
+        seq = (q->tid >= 0 && q->tid < h->n_ref) ? h->ref[q->tid] : NULL; len = seq ? h->reflen[q->tid] : 0;
+        pthread_mutex_unlock(&h->mu);
+        if(!seq) { snprintf(t_err, sizeof t_err, "dev_standin: reference for tid %d not uploaded", q->tid); return MDK_ERR_NOREF; }
+        if(slots[i] >= 0) {
+            sslot *s = slot_of(h, slots[i]);
+            if(!s || s->tid != q->tid || s->beg != q->beg || s->end != q->end) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_cytosines_group: the slot holds another chunk"); return MDK_ERR_ARG; }
+            rc[i] = md_dev_download(h, slots[i], &st);
+            if(rc[i]) continue;
+        }
+        end = q->end < len ? q->end : len;
+        c.key = q->key; c.tid = q->tid; c.n = 0; c.row = malloc(sizeof(yrow_t) * (size_t)((end > q->beg ? end - q->beg : 0) + 1));
+        if(!c.row) return MDK_ERR_NOMEM;
+        for(p = q->beg; p < end; p++) {
+            const int code = y_code(seq, len, p); yrow_t *r; int is_g;
+            if(!code || !h->ycfg.ctx_on[(code - 1) >> 1]) continue;
+            r = &c.row[c.n++]; is_g = !(code & 1);
+            r->pos = (int32_t)p + 1; r->strand = is_g ? -1 : 1; r->ctx = (uint8_t)((code - 1) >> 1); r->nm = r->nu = 0;
+            r->tri[0] = 'C'; r->tri[1] = is_g ? y_comp(y_at(seq, len, p - 1)) : y_fwd(y_at(seq, len, p + 1)); r->tri[2] = is_g ? y_comp(y_at(seq, len, p - 2)) : y_fwd(y_at(seq, len, p + 2));
+            while(k < st.n_sites && (int64_t)st.site[k].pos < p) k++;
+            if(k < st.n_sites && (int64_t)st.site[k].pos == p) {      /* the site's counts, unless the variant filter drops it */
+                const int var = st.var && h->ycfg.min_opposite_depth > 0 && st.var[k].noff >= (uint32_t)h->ycfg.min_opposite_depth && (double)st.var[k].nvar / (double)st.var[k].noff >= h->ycfg.max_variant_frac;
+                if(!var) { r->nm = (int32_t)st.site[k].nmeth; r->nu = (int32_t)st.site[k].nunmeth; }
+            }
+        }
+        if(h->n_ych == h->cap_ych) { h->cap_ych = h->cap_ych ? 2 * h->cap_ych : 64; h->ych = realloc(h->ych, sizeof(struct ychunk) * (size_t)h->cap_ych); if(!h->ych) return MDK_ERR_NOMEM; }
+        h->ych[h->n_ych++] = c;
+    }
+    return 0;
+}
+static int ychunk_cmp(const void *a, const void *b) { const struct ychunk *x = a, *y = b; return x->key < y->key ? -1 : x->key > y->key; }
+int md_dev_cytosines_finish(md_dev *h, md_cytosines_set **out) {
+    md_cytosines_set *r; int64_t n = 0, o = 0, k; int i;
+    if(!h || !out || !h->cyto_on) { snprintf(t_err, sizeof t_err, "dev_standin: md_dev_cytosines_finish"); return MDK_ERR_ARG; }
+    qsort(h->ych, (size_t)h->n_ych, sizeof(struct ychunk), ychunk_cmp);
+    for(i = 0; i < h->n_ych; i++) n += h->ych[i].n;
+    if(!(r = calloc(1, sizeof(*r)))) return MDK_ERR_NOMEM;
+    r->n = n; r->contig = malloc(4 * (size_t)(n + 1)); r->pos = malloc(4 * (size_t)(n + 1)); r->nm = malloc(4 * (size_t)(n + 1)); r->nu = malloc(4 * (size_t)(n + 1));
+    r->strand = malloc((size_t)n + 1); r->ctx = malloc((size_t)n + 1); r->tri = malloc(3 * (size_t)n + 1);
+    for(i = 0; i < h->n_ych; i++) for(k = 0; k < h->ych[i].n; k++, o++) {
+        const yrow_t *x = &h->ych[i].row[k];
+        r->contig[o] = h->ych[i].tid; r->pos[o] = x->pos; r->nm[o] = x->nm; r->nu[o] = x->nu; r->strand[o] = x->strand; r->ctx[o] = x->ctx; memcpy(r->tri + 3 * o, x->tri, 3);
+    }
+    cyto_drop(h);
+    *out = r;
+    return 0;
+}
+int64_t md_cytosines_set_count(const md_cytosines_set *c) { return c ? c->n : MDK_ERR_ARG; }
+int md_cytosines_set_copy(const md_cytosines_set *c, const md_cytosines_cols *d, int to_host) {
+    const size_t n = c ? (size_t)c->n : 0; (void)to_host;      /* ("device" memory is host memory here) */
+    if(!c || !d) return MDK_ERR_ARG;
+    if(d->contig) memcpy(d->contig, c->contig, 4 * n);
+    if(d->pos) memcpy(d->pos, c->pos, 4 * n);
+    if(d->strand) memcpy(d->strand, c->strand, n);
+    if(d->nmeth) memcpy(d->nmeth, c->nm, 4 * n);
+    if(d->nunmeth) memcpy(d->nunmeth, c->nu, 4 * n);
+    if(d->context) memcpy(d->context, c->ctx, n);
+    if(d->trinucleotide) memcpy(d->trinucleotide, c->tri, 3 * n);
+    return 0;
+}
+void md_cytosines_set_free(md_cytosines_set *c) { if(!c) return; free(c->contig); free(c->pos); free(c->nm); free(c->nu); free(c->strand); free(c->ctx); free(c->tri); free(c); }
 
 /* ---- perRead: the device's selection of a chunk's reads (perRead.c:178-183, k_prep_scan_ordered) restated over the uploaded records; the
  * counts (k_perread_raw's) are taken in order from the oracle's `perRead` output for the same command line (MDK_STANDIN_PERREAD), and each
