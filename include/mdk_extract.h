@@ -161,6 +161,11 @@ void mdk_session_close(mdk_session *s);
 int64_t mdk_calls_count(const mdk_calls *c);
 int  mdk_calls_n_contigs(const mdk_calls *c);
 const char *mdk_calls_contig_name(const mdk_calls *c, int i);
+/* what the run's command line said, for whoever writes the command's files from the rows (include/mdk_hip.h md_text_*): 1 when --mergeContext
+ * was on (the bedGraph header then says " merged"), and the contexts switched on as a bitmask (bit 0 CpG, 1 CHG, 2 CHH) -- the command writes a
+ * file, header only, also for a context that is on and has no row.  0 for the empty result of -h / --version; -1 for NULL */
+int  mdk_calls_merged(const mdk_calls *c);
+int  mdk_calls_contexts(const mdk_calls *c);
 int  mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host);
 void mdk_calls_free(mdk_calls *c);
 
@@ -233,6 +238,7 @@ int  mdk_session_cytosines(mdk_session *s, int argc, char *argv[], mdk_cytosines
 int64_t mdk_cytosines_count(const mdk_cytosines *c);
 int  mdk_cytosines_n_contigs(const mdk_cytosines *c);
 const char *mdk_cytosines_contig_name(const mdk_cytosines *c, int i);
+int  mdk_cytosines_contexts(const mdk_cytosines *c);      /* as mdk_calls_contexts: the contexts whose cytosines are rows (--mergeContext never reaches a report) */
 int  mdk_cytosines_copy(const mdk_cytosines *c, int column, void *dst, int to_host);
 void mdk_cytosines_free(mdk_cytosines *c);
 

@@ -121,6 +121,11 @@ class md_sites_dev(C.Structure):
     _fields_ = [("n_slots", C.c_int64), ("n_tiles", C.c_int32), ("d_site", C.c_void_p), ("d_var", C.c_void_p), ("d_seg", C.c_void_p)]
 
 
+class md_text_cols(C.Structure):
+    """md_calls_cols and md_cytosines_cols alike: seven device pointers, in the order of CALL_COLUMNS / CYTOSINE_COLUMNS"""
+    _fields_ = [(f"c{i}", C.c_void_p) for i in range(7)]
+
+
 class md_bench_result(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pileup", C.c_float), ("algo_bytes", C.c_uint64), ("n_sites", C.c_uint64),
                 ("tile", C.c_int32), ("n_tiles", C.c_int32), ("lds_bytes", C.c_int32)]
@@ -169,17 +174,18 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
-               "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free"]
+               "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_fill", "md_text_close"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
                    "mdk_plan_host_prepare_from", "mdk_plan_release_records", "mdk_plan_attach_device", "mdk_plan_detach_device",
                    "mbias_main", "mdk_cli_quiesce", "mdk_plan_open_mbias", "mdk_plan_mbias_outputs", "mdk_mbias_report",
                    "perRead_main", "mdk_plan_open_perread", "mdk_plan_emit_perread", "mdk_plan_emit_perread_raw", "mergeContext_main", "mdk_bind_to_device_node",
-                   "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_copy", "mdk_calls_free",
+                   "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_merged", "mdk_calls_contexts", "mdk_calls_copy", "mdk_calls_free",
                    "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free",
                    "mdk_mbias_suggest", "mdk_session_mbias", "mdk_bias_count", "mdk_bias_len", "mdk_bias_resubmitted", "mdk_bias_suggested", "mdk_bias_copy", "mdk_bias_free",
-                   "mdk_session_cytosines", "mdk_cytosines_count", "mdk_cytosines_n_contigs", "mdk_cytosines_contig_name", "mdk_cytosines_copy", "mdk_cytosines_free"]
+                   "mdk_session_cytosines", "mdk_cytosines_count", "mdk_cytosines_n_contigs", "mdk_cytosines_contig_name", "mdk_cytosines_contexts", "mdk_cytosines_copy", "mdk_cytosines_free"]
 
 _hip = None
 _ext = None
@@ -666,6 +672,47 @@ STRANDS = ("OT", "OB", "CTOT", "CTOB")
 CONTEXTS = ("CG", "CHG", "CHH")
 
 
+CONTEXT_FILES = ("CpG", "CHG", "CHH")                         # as the command names its files and headers
+TEXT_FORMATS = {"bedGraph": 0, "fraction": 1, "counts": 2, "methylKit": 3}       # MD_TEXT_* of include/mdk_hip.h
+TEXT_CYTOSINE_REPORT = 4
+TEXT_SUFFIX = (".bedGraph", ".meth.bedGraph", ".counts.bedGraph", ".methylKit")
+TEXT_WHAT = ("levels", "fractions", "counts")
+TEXT_BLOCK_ROWS = 1 << 22                                     # rows per block of `write` / `render`
+
+
+def _text_lib():
+    """libmdk_hip.so with the md_text_* entry points typed: resolved here, at the first render, and not when the library is loaded"""
+    L = lib_hip()
+    if not getattr(L, "_text_types", False):
+        L.md_text_open.argtypes = [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+        L.md_text_measure_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.md_text_measure_cytosines.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+        L.md_text_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.md_text_close.argtypes = [C.c_void_p]; L.md_text_close.restype = None
+        L._text_types = True
+    return L
+
+
+class _TextRenderer:
+    """one md_text: the contig names on the device (uploaded here, once) and the block table of the length scan"""
+
+    def __init__(self, L, device, contigs):
+        names = (C.c_char_p * max(len(contigs), 1))(*[os.fsencode(c) for c in contigs])
+        self.L, self.h = L, C.c_void_p()
+        rc = L.md_text_open(int(device), len(contigs), names, C.byref(self.h))
+        if rc:
+            self.h = None
+            raise _rc_error("md_text_open", rc, L.md_dev_last_error().decode())
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.md_text_close(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 def _session_lib():
     L = lib_extract()
     if not getattr(L, "_session_types", False):
@@ -681,6 +728,8 @@ def _session_lib():
             getattr(L, f"mdk_{kind}_contig_name").restype = C.c_char_p
             getattr(L, f"mdk_{kind}_copy").argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
             getattr(L, f"mdk_{kind}_free").argtypes = [C.c_void_p]
+        for f in ("mdk_calls_merged", "mdk_calls_contexts", "mdk_cytosines_contexts"):
+            getattr(L, f).argtypes = [C.c_void_p]
         L.mdk_session_mbias.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
         for f in ("count", "len", "resubmitted"):
             getattr(L, f"mdk_bias_{f}").argtypes = [C.c_void_p]
@@ -717,6 +766,81 @@ class _Columns:
         k = cls.KIND
         return cls([getattr(L, f"mdk_{k}_contig_name")(out, i).decode() for i in range(getattr(L, f"mdk_{k}_n_contigs")(out))], cols)
 
+    # ---- text on the device (include/mdk_hip.h md_text_*): Calls and Cytosines ----
+    def select(self, index):
+        """a copy with the rows ``column[index]`` of every column (a boolean mask, an index tensor, a slice), same contigs and options:
+        what ``render`` and ``write`` take just as they take the session's own result"""
+        import copy
+        c = copy.copy(self)
+        c._text = None
+        for name, _ in self.COLUMNS:
+            setattr(c, name, getattr(self, name)[index].contiguous())
+        return c
+
+    def _text_blocks(self, fmt, context, block_rows):
+        """the text of the rows, a block of at most ``block_rows`` rows at a time: uint8 tensors on the columns' device, made there by
+        k_text_len / k_text_fill"""
+        import torch
+        cols = [getattr(self, name) for name, _ in self.COLUMNS]
+        dev = cols[0].device
+        for t, (name, dt) in zip(cols, self.COLUMNS):
+            if t.device.type != "cuda":
+                raise MdkError(f"text is made on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+            if t.device != dev or t.dtype != getattr(torch, dt) or not t.is_contiguous() or t.shape[0] != cols[0].shape[0]:
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        block_rows = int(block_rows or os.environ.get("MDK_TEXT_BLOCK_ROWS") or TEXT_BLOCK_ROWS)        # (the variable is a test hook)
+        if not 1 <= block_rows <= 1 << 30:
+            raise MdkError("block_rows must be between 1 and 2^30")
+        L = _text_lib()
+        if getattr(self, "_text", None) is None:
+            self._text = _TextRenderer(L, dev.index or 0, self.contigs)
+        view = md_text_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
+        return self._text_iter(L, view, dev, fmt, context, block_rows)         # (checked before a file is opened; made block by block)
+
+    def _text_iter(self, L, view, dev, fmt, context, block_rows):
+        import torch
+        n = len(self)
+        for r0 in range(0, max(n, 1), block_rows):
+            r1 = min(n, r0 + block_rows)
+            torch.cuda.current_stream(dev).synchronize()         # the columns are complete, and nothing of torch's is queued on memory it hands out next
+            size = C.c_int64()
+            if fmt == TEXT_CYTOSINE_REPORT:
+                rc = L.md_text_measure_cytosines(self._text.h, C.byref(view), r0, r1, -1 if context is None else int(context), C.byref(size))
+            else:
+                rc = L.md_text_measure_calls(self._text.h, C.byref(view), r0, r1, fmt, -1 if context is None else int(context), C.byref(size))
+            if rc:
+                raise _rc_error("md_text_measure", rc, L.md_dev_last_error().decode())
+            out = torch.empty(size.value, dtype=torch.uint8, device=dev)
+            rc = L.md_text_fill(self._text.h, C.c_void_p(out.data_ptr()), size.value)
+            if rc:
+                raise _rc_error("md_text_fill", rc, L.md_dev_last_error().decode())
+            yield out
+
+    def _render(self, fmt, context, head, block_rows):
+        import torch
+        parts = [b for b in self._text_blocks(fmt, context, block_rows) if b.numel()]
+        dev = getattr(self, self.COLUMNS[0][0]).device
+        if head:
+            parts.insert(0, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
+        return torch.cat(parts) if len(parts) > 1 else parts[0] if parts else torch.empty(0, dtype=torch.uint8, device=dev)
+
+    def _write_file(self, path, fmt, context, head, block_rows):
+        """the header, then every block of text: one device-to-host copy into a pinned buffer each, appended to the file"""
+        import torch
+        pin, blocks = None, self._text_blocks(fmt, context, block_rows)
+        with open(path, "wb") as f:
+            f.write(head)
+            for b in blocks:
+                n = b.numel()
+                if not n:
+                    continue
+                if pin is None or pin.numel() < n:
+                    pin = torch.empty(n + n // 8, dtype=torch.uint8, pin_memory=True)
+                pin[:n].copy_(b, non_blocking=True)
+                torch.cuda.current_stream(b.device).synchronize()
+                f.write(memoryview(pin.numpy())[:n])
+        return path
+
 
 class Calls(_Columns):
     """The rows `extract` would print, as columns (one entry per call, in the order of the chunks of the schedule; within a context,
@@ -724,6 +848,55 @@ class Calls(_Columns):
     ``nmeth``/``nunmeth`` (int32), ``context`` (uint8: 0 CpG, 1 CHG, 2 CHH) and ``strand`` (int8: +1 C, -1 G, 0 a --mergeContext row)."""
     COLUMNS = CALL_COLUMNS
     KIND = "calls"
+
+    def __init__(self, contigs, columns, merged=False, contexts_on=(0, 1, 2)):
+        super().__init__(contigs, columns)
+        self.merged = bool(merged)                  # --mergeContext was on: the bedGraph headers say " merged"
+        self.contexts_on = tuple(contexts_on)       # the contexts switched on (0 CpG, 1 CHG, 2 CHH): `write` makes a file for each, rows or not
+
+    @classmethod
+    def _build(cls, L, out, cols):
+        c = super()._build(L, out, cols)
+        c.merged = L.mdk_calls_merged(out) == 1
+        c.contexts_on = tuple(k for k in range(3) if L.mdk_calls_contexts(out) >> k & 1)
+        return c
+
+    @staticmethod
+    def _format(fmt):
+        if fmt == "logit":
+            raise _rc_error("rendering --logit", RC_UNSUPPORTED, "its value goes through log(), which neither the host's nor the device's library rounds correctly: the command's bytes cannot be promised")
+        if fmt not in TEXT_FORMATS:
+            raise MdkError(f"unknown format {fmt!r}: one of {', '.join(TEXT_FORMATS)}")
+        return TEXT_FORMATS[fmt]
+
+    def header(self, fmt, context, prefix):
+        """the first line of the command's file for that format and context (csrc/host/mdk_plan.c), as bytes"""
+        code = self._format(fmt)
+        if fmt == "methylKit":
+            return b"chrBase\tchr\tbase\tstrand\tcoverage\tfreqC\tfreqT\n"
+        if prefix is None:
+            raise MdkError("the bedGraph header quotes the output prefix: give prefix=, or header=False")
+        return f'track type="bedGraph" description="{prefix} {CONTEXT_FILES[context]}{" merged" if self.merged else ""} methylation {TEXT_WHAT[code]}"\n'.encode()
+
+    def render(self, fmt="bedGraph", context=0, prefix=None, header=True, block_rows=None):
+        """The bytes of the file `extract -o prefix` writes for one context (0 CpG, 1 CHG, 2 CHH), as a uint8 tensor on the columns' device,
+        made there (csrc/mdk_text.hip) from whatever the columns hold now -- the session's rows, or a filtered or re-ordered ``select``.
+        ``fmt``: "bedGraph" (the default output), "fraction" (--fraction), "counts" (--counts) or "methylKit" (--methylKit); byte for byte the
+        command's text, %f and %6.2f included.  "logit" raises MdkError with rc -23: --logit's value goes through log(), which is not
+        correctly rounded on either side, so its bytes cannot be promised.  Rows of other contexts and rows without coverage give no line;
+        a methylKit line of a --mergeContext row (strand 0) is an error, as the combination is for the command.  ``header=False`` leaves the
+        first line out.  CPU tensors raise MdkError: there is no CPU path."""
+        code = self._format(fmt)
+        return self._render(code, int(context), self.header(fmt, int(context), prefix) if header else b"", block_rows)
+
+    def write(self, prefix, fmt="bedGraph", directory=None, block_rows=None):
+        """The command's file set under the command's names -- <prefix>_CpG.bedGraph, .meth.bedGraph (fraction), .counts.bedGraph,
+        .methylKit --, one file per context in ``contexts_on``, header-only where there is no row; in ``directory`` if given.  The text is
+        made on the device in blocks of ``block_rows`` rows (default 2^22), each copied to the host once and appended: the extra device and
+        pinned memory is one block's text, not the file's.  Returns the paths."""
+        code = self._format(fmt)
+        return [self._write_file(os.path.join(directory, f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}") if directory is not None else f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}",
+                                 code, k, self.header(fmt, k, prefix), block_rows) for k in self.contexts_on]
 
     def rows(self, context=None):
         """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
@@ -804,6 +977,7 @@ class Cytosines(_Columns):
     matrix."""
     COLUMNS = CYTOSINE_COLUMNS
     KIND = "cytosines"
+    contexts_on = (0, 1, 2)
 
     @classmethod
     def _sizes(cls, L, out, n):
@@ -812,7 +986,19 @@ class Cytosines(_Columns):
     @classmethod
     def _build(cls, L, out, cols):
         cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
-        return super()._build(L, out, cols)
+        c = super()._build(L, out, cols)
+        c.contexts_on = tuple(k for k in range(3) if L.mdk_cytosines_contexts(out) >> k & 1)      # the contexts whose cytosines are rows
+        return c
+
+    def render(self, block_rows=None):
+        """The bytes of <prefix>.cytosine_report.txt (no header), as a uint8 tensor on the columns' device, made there from whatever the
+        columns hold now.  CPU tensors raise MdkError."""
+        return self._render(TEXT_CYTOSINE_REPORT, None, b"", block_rows)
+
+    def write(self, prefix, directory=None, block_rows=None):
+        """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  Returns the path."""
+        name = f"{prefix}.cytosine_report.txt"
+        return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows)
 
     def rows(self):
         """(chrom, pos, "+"/"-", nmeth, nunmeth, "CG"/"CHG"/"CHH", trinucleotide) tuples on the host: the seven fields of a line"""
@@ -826,7 +1012,8 @@ class Session:
     command line as for run_cli (without the command name).  The rows never pass through text: they are compacted on the device
     (k_calls_compact) and copied device to device into tensors torch allocated on ``torch.device("cuda", device)``; with
     ``device_tensors=False`` into CPU tensors instead.  --fraction/--counts/--logit/--methylKit/--cytosine_report are refused (rc -23),
-    -o is ignored; any non-zero return code raises MdkError with ``.rc``.  ``perread(args) -> Reads`` runs `perRead` command lines on the
+    -o is ignored; any non-zero return code raises MdkError with ``.rc``.  The files come from the result: ``Calls.write(prefix, fmt)`` and
+    ``Cytosines.write(prefix)`` make the command's text on the device, byte for byte (the format is chosen there, not on the command line).  ``perread(args) -> Reads`` runs `perRead` command lines on the
     same handle, ``mbias(args) -> Bias`` `mbias` ones, and ``cytosine_report(args) -> Cytosines`` gives the one output of `extract` that
     ``extract`` refuses: a row for every cytosine of the reference."""
 
@@ -909,8 +1096,8 @@ class Session:
             pass
 
 
-def _rc_error(what, rc):
-    msg = "option not available through a session" if rc == RC_UNSUPPORTED else MDK_ERR.get(rc, "see stderr")
+def _rc_error(what, rc, detail=None):
+    msg = detail or ("option not available through a session" if rc == RC_UNSUPPORTED else MDK_ERR.get(rc, "see stderr"))
     e = MdkError(f"{what} failed: rc {rc} ({msg})")
     e.rc = rc
     return e

@@ -443,6 +443,8 @@ int mdk_session_extract(mdk_session *s, int argc, char *argv[], mdk_calls **out)
 int64_t mdk_calls_count(const mdk_calls *c) { return c ? c->r.n : -1; }
 int mdk_calls_n_contigs(const mdk_calls *c) { return result_n_contigs(c ? &c->r : NULL); }
 const char *mdk_calls_contig_name(const mdk_calls *c, int i) { return result_contig_name(c ? &c->r : NULL, i); }
+int mdk_calls_merged(const mdk_calls *c) { return c ? c->r.merged : -1; }
+int mdk_calls_contexts(const mdk_calls *c) { return c ? c->r.contexts : -1; }
 int mdk_calls_copy(const mdk_calls *c, int column, void *dst, int to_host) {
     md_calls_cols d; memset(&d, 0, sizeof(d));
     if(!c || !dst || column < 0 || column > MDK_CALLS_STRAND) return MDK_ERR_ARG;
@@ -464,6 +466,7 @@ int mdk_session_cytosines(mdk_session *s, int argc, char *argv[], mdk_cytosines 
 int64_t mdk_cytosines_count(const mdk_cytosines *c) { return c ? c->r.n : -1; }
 int mdk_cytosines_n_contigs(const mdk_cytosines *c) { return result_n_contigs(c ? &c->r : NULL); }
 const char *mdk_cytosines_contig_name(const mdk_cytosines *c, int i) { return result_contig_name(c ? &c->r : NULL, i); }
+int mdk_cytosines_contexts(const mdk_cytosines *c) { return c ? c->r.contexts : -1; }
 int mdk_cytosines_copy(const mdk_cytosines *c, int column, void *dst, int to_host) {
     md_cytosines_cols d; memset(&d, 0, sizeof(d));
     if(!c || !dst || column < 0 || column > MDK_CYTOSINES_TRINUCLEOTIDE) return MDK_ERR_ARG;

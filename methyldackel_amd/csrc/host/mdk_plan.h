@@ -143,7 +143,7 @@ struct mdk_session { int device; md_dev *dev; md_dev_cfg cfg; };
 MDK_LOCAL void session_geometry(md_dev_cfg *cfg);              /* (mdk_extract.c) the slots and streams of every session run, whatever its command: switching commands resets the handle */
 MDK_LOCAL void session_device(mdk_session *S, devopen_t *d);   /* the session's handle for a run with d->cfg: opened at the first run, reset before every later one */
 /* what a session run hands back, whatever its command (mdk_session.c): the rows' device set, their count, the contig names of the BAM header */
-typedef struct { void *set; int64_t n; int n_contigs; char **names; } mdk_result;
+typedef struct { void *set; int64_t n; int n_contigs; char **names; int merged, contexts; } mdk_result;      /* merged, contexts: what the command line said (--mergeContext; bit k: context k on) */
 struct mdk_calls { mdk_result r; };
 struct mdk_reads { mdk_result r; int64_t n_bytes; };
 struct mdk_bias { mdk_result r; int len, redone, bounds[16], has[4]; };

@@ -41,6 +41,7 @@ MDK_LOCAL int session_result(int ret, int frc, const mdk_plan *p, size_t size, v
     if(r) r->names = calloc((size_t)nt + 1, sizeof(char *));
     if(!r || !r->names) { free(r); return -5; }
     r->set = set; r->n = n; r->n_contigs = nt;
+    r->merged = p->o.merge ? 1 : 0; r->contexts = (p->o.ctx_on[0] ? 1 : 0) | (p->o.ctx_on[1] ? 2 : 0) | (p->o.ctx_on[2] ? 4 : 0);
     for(i = 0; i < nt; i++) r->names[i] = strdup(p->bam->target_name[i]);
     *out = r;
     return 0;

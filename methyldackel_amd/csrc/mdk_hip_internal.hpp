@@ -200,6 +200,20 @@ __device__ __forceinline__ bool site_is_variant(int32_t min_opp, double max_vf, 
     return has_var && min_opp > 0 && v.noff >= (uint32_t)min_opp && (double)v.nvar / (double)v.noff >= max_vf;
 }
 
+// exclusive scan of v over the workgroup (WGS threads, waves of 64; mdk_reads.hip, mdk_text.hip): wave scan with __shfl_up, wave totals through LDS
+template <int WGS, typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T *wtot, T &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T x = v;
+    for(int d = 1; d < 64; d <<= 1) { const T y = __shfl_up(x, d, 64); if(lane >= d) x += y; }
+    if(lane == 63) wtot[wave] = x;
+    __syncthreads();
+    T before = 0; total = 0;
+    for(int w = 0; w < WGS / 64; w++) { const T t = wtot[w]; if(w < wave) before += t; total += t; }
+    __syncthreads();                 // (wtot may be rewritten by the caller's next round)
+    return before + x - v;
+}
+
 // MDK_HOST_PROFILE=1: where the host threads' time inside the library goes (seconds and calls per site), printed by md_dev_profile_dump
 enum { PF_UP_SYNC = 0, PF_UP_ALLOC, PF_UP_COPY, PF_LAUNCH, PF_FIN_WAIT, PF_DL_COPY, PF_DL_ORDER, PF_SETREF, PF_PIECE_SUBMIT, PF_PIECE_WAIT, PF_GRP_DEV, PF_GRP_TURN, PF_N };
 MDK_HIDDEN bool mdk_prof_on();

@@ -43,20 +43,6 @@ struct md_reads_set { int device = 0; int64_t n = 0, n_bytes = 0; ReadsTables t;
 // ------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------
-// exclusive scan of v over the workgroup (WGS threads, waves of 64): wave scan with __shfl_up, wave totals through LDS
-template <int WGS>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wtot, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-    for(int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if(lane >= d) x += y; }
-    if(lane == 63) wtot[wave] = x;
-    __syncthreads();
-    uint32_t before = 0; total = 0;
-    for(int w = 0; w < WGS / 64; w++) { const uint32_t t = wtot[w]; if(w < wave) before += t; total += t; }
-    __syncthreads();                 // (wtot may be rewritten by the caller's next round)
-    return before + x - v;
-}
-
 struct KReadsScan { const uint8_t *raw; uint64_t raw_span; const uint32_t *rec_at, *aidx; PrepCounters *cnt; uint32_t *loc, *boff; };
 
 // the name of the record at `o`: l_read_name bytes up to the first NUL, never past the chunk's records

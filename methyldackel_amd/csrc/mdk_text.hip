@@ -1,0 +1,213 @@
+// mdk_text.hip -- the text of `extract`'s files made on the device from columns (include/mdk_hip.h, "text on the device").
+//
+// The rows of a session's Calls or Cytosines -- or any column tensors in those layouts, filtered or re-ordered -- become the bytes of a
+// bedGraph, a methylKit file or a cytosine report without leaving the device: one device-to-host copy per block of rows then goes to disk.
+// The characters are those of csrc/host/mdk_emit.c put_site, from the integer arithmetic of mdk_text_core.h (exact %f and %6.2f included).
+// Measure first, fill second, as k_cyto_count / k_cyto_fill size the report's rows:
+//   k_text_len     a row per lane, 256 rows per workgroup: the length of the row's line (name length + digit counts + constants; 0 for a row
+//                  of another context, or without coverage in a format that prints none), scanned inside the workgroup (wave64 __shfl_up,
+//                  wave totals through LDS); the workgroup's total to a table
+//   k_text_blocks  one workgroup: the exclusive scan of those totals as int64 offsets, and the byte count of the whole text
+//   k_text_fill    the same lengths and scan again (cheaper than a per-row offset written and read back), then the workgroup ASSEMBLES ITS
+//                  LINES IN LDS -- every lane writes its line at its scanned offset -- and the whole workgroup streams that image out: 16-byte
+//                  stores to 16-byte aligned addresses, consecutive lanes consecutive 16 bytes.  The image sits in LDS at the destination's
+//                  misalignment, so an LDS quad IS a global quad; the up to 15 bytes before the first and after the last full quad of a
+//                  workgroup's text go out as bytes.  (k_reads_names' form -- a byte per lane, each found by a binary search -- measured
+//                  ~41 GB/s.)  A workgroup whose text is longer than the image (contig names of hundreds of bytes) writes its lines straight
+//                  to global memory instead.
+// k_text_fill re-checks every workgroup's total against what k_text_len recorded: columns that changed between the two calls end the fill
+// with an error instead of a write past the buffer.
+#include "mdk_hip_internal.hpp"
+#include "mdk_text_core.h"
+#include <string>
+
+#define TEXT_WG 256
+#define TEXT_SCAN_WG 1024
+#define TEXT_LDS_BYTES (24 * 1024)        // the image: 96 bytes per row (a default bedGraph line of a human contig is ~35, a methylKit one ~55)
+#define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
+enum { TEXT_E_CONTIG = 1, TEXT_E_STRAND0 = 2, TEXT_E_CONTEXT = 4, TEXT_E_CHANGED = 8 };
+
+struct TextStatus { int64_t total; uint32_t err, pad; };
+// the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
+struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
+struct KText {
+    TextView v; int64_t r0; uint32_t n; int32_t fmt, context, n_contigs;
+    const uint32_t *name_off; const uint8_t *names;          // name c = names[name_off[c] .. name_off[c + 1])
+    uint32_t *btot; int64_t *boff; TextStatus *st;
+    uint8_t *dst; int64_t bytes;
+};
+
+struct md_text {
+    int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
+    uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
+    uint32_t *d_btot = nullptr; int64_t *d_boff = nullptr; size_t cap_blocks = 0;
+    TextStatus *d_st = nullptr, *h_st = nullptr;
+    KText K; bool measured = false;
+};
+
+// row i of the range: the length of its line (0: no line) and what txt_put_line needs
+__device__ __forceinline__ uint32_t text_row(const KText &K, uint32_t i, txt_row &r, const uint8_t *&name, uint32_t &name_len, uint32_t &err) {
+    if(i >= K.n) return 0;
+    const int64_t at = K.r0 + i;
+    const uint32_t ctx = K.v.ctx[at];
+    if(K.context >= 0 && ctx != (uint32_t)K.context) return 0;
+    const int32_t c = K.v.contig[at];
+    if(c < 0 || c >= K.n_contigs) { err |= TEXT_E_CONTIG; return 0; }
+    r.a = K.v.a[at]; r.b = K.v.b ? K.v.b[at] : 0; r.m = (uint32_t)K.v.m[at]; r.u = (uint32_t)K.v.u[at];
+    r.strand = K.v.strand[at]; r.context = ctx; r.tri = K.v.tri ? K.v.tri + 3 * at : nullptr;
+    if(!txt_row_printed(K.fmt, r)) return 0;
+    if(K.fmt == MD_TEXT_METHYLKIT && r.strand == 0) { err |= TEXT_E_STRAND0; return 0; }
+    if(K.fmt == MD_TEXT_CYTOSINE_REPORT && ctx > 2u) { err |= TEXT_E_CONTEXT; return 0; }
+    const uint32_t o = K.name_off[c];
+    name = K.names + o; name_len = K.name_off[c + 1] - o;
+    return txt_line_len(K.fmt, name_len, r);
+}
+
+__global__ __launch_bounds__(TEXT_WG) void k_text_len(const KText K) {
+    __shared__ uint32_t wtot[TEXT_WG / 64];
+    txt_row r; const uint8_t *name = nullptr; uint32_t name_len = 0, err = 0, total;
+    const uint32_t len = text_row(K, blockIdx.x * TEXT_WG + threadIdx.x, r, name, name_len, err);
+    if(err) atomicOr(&K.st->err, err);
+    (void)block_excl_scan<TEXT_WG>(len, wtot, total);
+    if(threadIdx.x == 0) K.btot[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(TEXT_SCAN_WG) void k_text_blocks(const KText K) {
+    __shared__ int64_t wtot[TEXT_SCAN_WG / 64];
+    const uint32_t nb = (K.n + TEXT_WG - 1) / TEXT_WG;
+    int64_t carry = 0;
+    for(uint32_t b0 = 0; b0 < nb; b0 += TEXT_SCAN_WG) {          // (uniform trip count: every thread takes part in every scan)
+        const uint32_t b = b0 + threadIdx.x;
+        const int64_t v = b < nb ? (int64_t)K.btot[b] : 0;
+        int64_t total;
+        const int64_t ex = block_excl_scan<TEXT_SCAN_WG>(v, wtot, total);
+        if(b < nb) K.boff[b] = carry + ex;
+        carry += total;
+    }
+    if(threadIdx.x == 0) K.st->total = carry;
+}
+
+__global__ __launch_bounds__(TEXT_WG) void k_text_fill(const KText K) {
+    __shared__ uint32_t wtot[TEXT_WG / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t img[TEXT_LDS_BYTES + 16];
+    txt_row r; const uint8_t *name = nullptr; uint32_t name_len = 0, err = 0, total;
+    const uint32_t len = text_row(K, blockIdx.x * TEXT_WG + threadIdx.x, r, name, name_len, err);
+    const uint32_t ex = block_excl_scan<TEXT_WG>(len, wtot, total);
+    const int64_t off = K.boff[blockIdx.x];
+    // what k_text_len measured for this workgroup, inside the buffer: anything else means the columns are not the measured ones
+    if(total != K.btot[blockIdx.x] || off < 0 || off + (int64_t)total > K.bytes) { if(threadIdx.x == 0) atomicOr(&K.st->err, (uint32_t)TEXT_E_CHANGED); return; }
+    if(total == 0) return;
+    uint8_t *const g = K.dst + off;
+    if(total > TEXT_LDS_BYTES) {             // longer than the image: every lane its own line, straight to global memory
+        if(len) txt_put_line((char *)g + ex, K.fmt, name, name_len, r);
+        return;
+    }
+    const txt_image_plan P = txt_plan_image((uint64_t)(uintptr_t)g, total);         // img[P.sh + i] is g[i]: img quad k is the aligned global quad k of g - P.sh
+    if(len) txt_put_line((char *)img + P.sh + ex, K.fmt, name, name_len, r);
+    __syncthreads();
+    uint8_t *const g0 = g - P.sh;
+    uint4 *const gq = (uint4 *)g0; const uint4 *const lq = (const uint4 *)img;
+    for(uint32_t k = P.quad0 + threadIdx.x; k < P.quad1; k += TEXT_WG) gq[k] = lq[k];
+    if(P.sh + threadIdx.x < P.head_end) g0[P.sh + threadIdx.x] = img[P.sh + threadIdx.x];           // (at most 15 bytes each: one pass of the workgroup)
+    if(P.tail0 + threadIdx.x < P.end) g0[P.tail0 + threadIdx.x] = img[P.tail0 + threadIdx.x];
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+extern "C" int md_text_open(int device, int32_t n_contigs, const char *const *names, md_text **out) {
+    if(!out || device < 0 || n_contigs < 0 || (n_contigs && !names)) return fail(MDK_ERR_ARG, "md_text_open", hipSuccess);
+    *out = nullptr;
+    std::vector<uint32_t> off((size_t)n_contigs + 1, 0u); std::string bytes;
+    for(int32_t i = 0; i < n_contigs; i++) {
+        const size_t l = names[i] ? strlen(names[i]) : 0;
+        if(!names[i] || l > MD_TEXT_NAME_MAX) { snprintf(mdk_err_buf(), MDK_ERR_BYTES, "md_text_open: contig %d has no name or one longer than %d bytes", (int)i, MD_TEXT_NAME_MAX); return MDK_ERR_ARG; }
+        bytes.append(names[i], l); off[(size_t)i + 1] = (uint32_t)bytes.size();
+    }
+    HIPCHK(hipSetDevice(device));
+    md_text *t = new md_text(); t->device = device; t->n_contigs = n_contigs;
+    hipError_t e = hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking);
+    if(e == hipSuccess) e = hipMalloc((void **)&t->d_name_off, off.size() * 4);
+    if(e == hipSuccess) e = hipMalloc((void **)&t->d_names, bytes.size() + 16);
+    if(e == hipSuccess) e = hipMalloc((void **)&t->d_st, sizeof(TextStatus));
+    if(e == hipSuccess) e = hipHostMalloc((void **)&t->h_st, sizeof(TextStatus), hipHostMallocDefault);
+    if(e == hipSuccess) e = hipMemcpy(t->d_name_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
+    if(e == hipSuccess && !bytes.empty()) e = hipMemcpy(t->d_names, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+    if(e != hipSuccess) { md_text_close(t); return fail(MDK_ERR_HIP, "md_text_open", e); }
+    *out = t;
+    return 0;
+}
+
+extern "C" void md_text_close(md_text *t) {
+    if(!t) return;
+    (void)hipSetDevice(t->device);
+    if(t->st) { (void)hipStreamSynchronize(t->st); (void)hipStreamDestroy(t->st); }
+    (void)hipFree(t->d_name_off); (void)hipFree(t->d_names); (void)hipFree(t->d_btot); (void)hipFree(t->d_boff); (void)hipFree(t->d_st);
+    if(t->h_st) (void)hipHostFree(t->h_st);
+    delete t;
+}
+
+// the status block back on the host; what the kernels flagged as this call's error
+static int text_status(md_text *t, const char *what) {
+    HIPCHK(hipMemcpyAsync(t->h_st, t->d_st, sizeof(TextStatus), hipMemcpyDeviceToHost, t->st));
+    HIPCHK(hipStreamSynchronize(t->st));
+    const uint32_t err = t->h_st->err;
+    if(!err) return 0;
+    snprintf(mdk_err_buf(), MDK_ERR_BYTES, "%s: %s", what,
+             err & TEXT_E_CHANGED ? "the columns are not the ones that were measured" :
+             err & TEXT_E_CONTIG ? "a row's contig is not an index into the renderer's names" :
+             err & TEXT_E_STRAND0 ? "a methylKit line needs the row's strand: --mergeContext rows (strand 0) have none" : "a row's context is not 0, 1 or 2");
+    return MDK_ERR_ARG;
+}
+
+static int text_measure(md_text *t, const TextView &v, int64_t r0, int64_t r1, int fmt, int context, int64_t *bytes, const char *what) {
+    if(!t || !bytes || r0 < 0 || r1 < r0 || r1 - r0 > TEXT_MAX_ROWS || context < -1 || context > 2) return fail(MDK_ERR_ARG, what, hipSuccess);
+    *bytes = 0; t->measured = false;
+    const uint32_t n = (uint32_t)(r1 - r0), nb = (n + TEXT_WG - 1) / TEXT_WG;
+    if(n && (!v.contig || !v.a || !v.m || !v.u || !v.ctx || !v.strand || (fmt == MD_TEXT_CYTOSINE_REPORT ? !v.tri : !v.b))) return fail(MDK_ERR_ARG, what, hipSuccess);
+    HIPCHK(hipSetDevice(t->device));
+    if(nb > t->cap_blocks) {
+        (void)hipFree(t->d_btot); (void)hipFree(t->d_boff); t->d_btot = nullptr; t->d_boff = nullptr; t->cap_blocks = 0;
+        const size_t want = (size_t)nb + nb / 4 + 64;
+        hipError_t e = hipMalloc((void **)&t->d_btot, want * 4);
+        if(e == hipSuccess) e = hipMalloc((void **)&t->d_boff, want * 8);
+        if(e != hipSuccess) return fail(MDK_ERR_NOMEM, "hipMalloc(text block table)", e);
+        t->cap_blocks = want;
+    }
+    KText &K = t->K;
+    K.v = v; K.r0 = r0; K.n = n; K.fmt = fmt; K.context = context; K.n_contigs = t->n_contigs; K.name_off = t->d_name_off; K.names = t->d_names;
+    K.btot = t->d_btot; K.boff = t->d_boff; K.st = t->d_st; K.dst = nullptr; K.bytes = 0;
+    HIPCHK(hipMemsetAsync(t->d_st, 0, sizeof(TextStatus), t->st));
+    if(nb) {
+        hipLaunchKernelGGL(k_text_len, dim3(nb), dim3(TEXT_WG), 0, t->st, K);
+        hipLaunchKernelGGL(k_text_blocks, dim3(1), dim3(TEXT_SCAN_WG), 0, t->st, K);
+        HIPCHK(hipGetLastError());
+    }
+    { const int rc = text_status(t, what); if(rc) return rc; }
+    K.bytes = t->h_st->total; t->measured = true;
+    *bytes = K.bytes;
+    return 0;
+}
+
+extern "C" int md_text_measure_calls(md_text *t, const md_calls_cols *c, int64_t r0, int64_t r1, int fmt, int context, int64_t *bytes) {
+    if(!c || fmt < MD_TEXT_BEDGRAPH || fmt > MD_TEXT_METHYLKIT) return fail(MDK_ERR_ARG, "md_text_measure_calls", hipSuccess);
+    const TextView v = {c->contig, c->start, c->end, c->nmeth, c->nunmeth, c->context, c->strand, nullptr};
+    return text_measure(t, v, r0, r1, fmt, context, bytes, "md_text_measure_calls");
+}
+
+extern "C" int md_text_measure_cytosines(md_text *t, const md_cytosines_cols *c, int64_t r0, int64_t r1, int context, int64_t *bytes) {
+    if(!c) return fail(MDK_ERR_ARG, "md_text_measure_cytosines", hipSuccess);
+    const TextView v = {c->contig, c->pos, nullptr, c->nmeth, c->nunmeth, c->context, c->strand, c->trinucleotide};
+    return text_measure(t, v, r0, r1, MD_TEXT_CYTOSINE_REPORT, context, bytes, "md_text_measure_cytosines");
+}
+
+extern "C" int md_text_fill(md_text *t, void *dst, int64_t bytes) {
+    if(!t || !t->measured || bytes != t->K.bytes || (bytes && !dst)) return fail(MDK_ERR_ARG, "md_text_fill: md_text_measure_* first, then a buffer of exactly the measured size", hipSuccess);
+    if(!bytes) return 0;
+    HIPCHK(hipSetDevice(t->device));
+    KText &K = t->K; K.dst = (uint8_t *)dst;
+    HIPCHK(hipMemsetAsync(t->d_st, 0, sizeof(TextStatus), t->st));
+    hipLaunchKernelGGL(k_text_fill, dim3((K.n + TEXT_WG - 1) / TEXT_WG), dim3(TEXT_WG), 0, t->st, K);
+    HIPCHK(hipGetLastError());
+    return text_status(t, "md_text_fill");
+}
