@@ -471,12 +471,14 @@ int64_t md_cytosines_set_count(const md_cytosines_set *c);
 int  md_cytosines_set_copy(const md_cytosines_set *c, const md_cytosines_cols *dst, int to_host);
 void md_cytosines_set_free(md_cytosines_set *c);
 
-/* ---- text on the device: the lines of `extract`'s files from columns (csrc/mdk_text.hip, csrc/mdk_text_core.h) ----
- * A renderer turns rows held as DEVICE-resident columns in the layouts above (md_calls_cols, md_cytosines_cols: a session's result, or any
+/* ---- text on the device: the lines of `extract`'s and `perRead`'s files from columns (csrc/mdk_text.hip, csrc/mdk_text_core.h) ----
+ * A renderer turns rows held as DEVICE-resident columns in the layouts above (md_calls_cols, md_cytosines_cols, md_reads_cols: a session's result, or any
  * arrays of those types -- filtered, re-ordered, concatenated) into the bytes csrc/host/mdk_emit.c put_site prints for them:
  *   MD_TEXT_BEDGRAPH   chrom start end (int)(100 m / cov) m u        MD_TEXT_FRACTION   chrom start end %f of m / cov
  *   MD_TEXT_COUNTS     chrom start end cov                           MD_TEXT_METHYLKIT  chrom.start+1 chrom start+1 F|R cov %6.2f %6.2f
  *   MD_TEXT_CYTOSINE_REPORT (md_text_measure_cytosines)  chrom pos +|- m u CG|CHG|CHH trinucleotide
+ *   MD_TEXT_PERREAD (md_text_measure_reads)  name chrom pos V cov, as csrc/host/mdk_cmd_perread.c prints a read: cov = m + u, V = %f of
+ *                      100 m / cov, or the characters 0.0 when cov == 0.  Every row has a line, covered or not
  * byte for byte what the command writes, %f and %6.2f included (exact, from integer arithmetic).  --logit has no format here: its value goes
  * through log(), which neither glibc nor the device library rounds correctly, so equal bytes cannot be promised.  Headers are not written.
  * A renderer belongs to a device and a contig name table (copied to the device once, by md_text_open; a name longer than 255 bytes is refused
@@ -485,20 +487,32 @@ void md_cytosines_set_free(md_cytosines_set *c);
  *                      no line (-1: every row); in the four call formats a row with nmeth + nunmeth == 0 gives none either (the command prints
  *                      none).  MDK_ERR_ARG, with md_dev_last_error, for a contig index outside the name table, a MD_TEXT_METHYLKIT row with
  *                      strand 0 (a --mergeContext row: the command refuses that combination) or a report row whose context is above 2;
+ *   md_text_measure_reads  the same for rows [r0, r1) of md_reads_cols, whose name_off holds at least r1 + 1 entries and whose name_bytes holds
+ *                      n_name_bytes bytes.  MDK_ERR_ARG for a contig index outside the name table, a name offset outside [0, n_name_bytes],
+ *                      offsets that decrease inside the range, or a name longer than 255 bytes: no name is read before these are checked;
  *   md_text_fill       the text of the range measured last into `dst`, DEVICE memory of exactly *bytes bytes (any alignment).  Columns that
  *                      changed since the measure are detected per workgroup and end the call with MDK_ERR_ARG; nothing is written past dst.
  * Both work on the renderer's own stream and are synchronous: the columns must be complete when md_text_measure_* is called (a caller that
  * filled them on a stream of its own waits for that stream first), and dst holds the text when md_text_fill returns.  One thread at a time
- * per renderer.  The renderer owns the name table and a table of one entry per 256 rows, until md_text_close. */
+ * per renderer.  The renderer owns the name table and a table of one entry per 256 rows, until md_text_close.
+ *   md_text_gather_names  the ragged gather of read names (no text): name index[i] of the source -- src_bytes[src_off[j] .. src_off[j + 1]),
+ *                      n_src names in n_src_bytes bytes -- to dst_bytes[dst_off[i] .. dst_off[i + 1]) for i in [0, n).  index has n int64
+ *                      entries in any order, repeats allowed; dst_off has n + 1 entries, the scan of the selected lengths, made by the
+ *                      caller; every array is DEVICE memory.  Same stream, same rules.  MDK_ERR_ARG for an index outside [0, n_src), source
+ *                      offsets as refused above, or destination offsets that are not that scan inside [0, n_dst_bytes]; a workgroup with
+ *                      such a row writes nothing, and nothing is read or written outside the arrays. */
 #ifndef MD_TEXT_FORMATS
 #define MD_TEXT_FORMATS
-enum { MD_TEXT_BEDGRAPH = 0, MD_TEXT_FRACTION, MD_TEXT_COUNTS, MD_TEXT_METHYLKIT, MD_TEXT_CYTOSINE_REPORT, MD_TEXT_N_FORMATS };
+enum { MD_TEXT_BEDGRAPH = 0, MD_TEXT_FRACTION, MD_TEXT_COUNTS, MD_TEXT_METHYLKIT, MD_TEXT_CYTOSINE_REPORT, MD_TEXT_PERREAD, MD_TEXT_N_FORMATS };
 #endif
 typedef struct md_text md_text;
 int  md_text_open(int device, int32_t n_contigs, const char *const *names, md_text **out);
 int  md_text_measure_calls(md_text *t, const md_calls_cols *cols, int64_t r0, int64_t r1, int fmt, int context, int64_t *bytes);
 int  md_text_measure_cytosines(md_text *t, const md_cytosines_cols *cols, int64_t r0, int64_t r1, int context, int64_t *bytes);
+int  md_text_measure_reads(md_text *t, const md_reads_cols *cols, int64_t n_name_bytes, int64_t r0, int64_t r1, int64_t *bytes);
 int  md_text_fill(md_text *t, void *dst, int64_t bytes);
+int  md_text_gather_names(md_text *t, const int64_t *src_off, const uint8_t *src_bytes, int64_t n_src, int64_t n_src_bytes,
+                          const int64_t *index, int64_t n, const int64_t *dst_off, uint8_t *dst_bytes, int64_t n_dst_bytes);
 void md_text_close(md_text *t);
 
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`

@@ -126,6 +126,10 @@ class md_text_cols(C.Structure):
     _fields_ = [(f"c{i}", C.c_void_p) for i in range(7)]
 
 
+class md_reads_cols(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("contig", "pos", "nmeth", "nunmeth", "name_off", "name_bytes")]
+
+
 class md_bench_result(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pileup", C.c_float), ("algo_bytes", C.c_uint64), ("n_sites", C.c_uint64),
                 ("tile", C.c_int32), ("n_tiles", C.c_int32), ("lds_bytes", C.c_int32)]
@@ -175,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_fill", "md_text_close"]
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
@@ -675,6 +679,7 @@ CONTEXTS = ("CG", "CHG", "CHH")
 CONTEXT_FILES = ("CpG", "CHG", "CHH")                         # as the command names its files and headers
 TEXT_FORMATS = {"bedGraph": 0, "fraction": 1, "counts": 2, "methylKit": 3}       # MD_TEXT_* of include/mdk_hip.h
 TEXT_CYTOSINE_REPORT = 4
+TEXT_PERREAD = 5
 TEXT_SUFFIX = (".bedGraph", ".meth.bedGraph", ".counts.bedGraph", ".methylKit")
 TEXT_WHAT = ("levels", "fractions", "counts")
 TEXT_BLOCK_ROWS = 1 << 22                                     # rows per block of `write` / `render`
@@ -687,7 +692,9 @@ def _text_lib():
         L.md_text_open.argtypes = [C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
         L.md_text_measure_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         L.md_text_measure_cytosines.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+        L.md_text_measure_reads.argtypes = [C.c_void_p, C.POINTER(md_reads_cols), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
         L.md_text_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.md_text_gather_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
         L.md_text_close.argtypes = [C.c_void_p]; L.md_text_close.restype = None
         L._text_types = True
     return L
@@ -766,7 +773,7 @@ class _Columns:
         k = cls.KIND
         return cls([getattr(L, f"mdk_{k}_contig_name")(out, i).decode() for i in range(getattr(L, f"mdk_{k}_n_contigs")(out))], cols)
 
-    # ---- text on the device (include/mdk_hip.h md_text_*): Calls and Cytosines ----
+    # ---- text on the device (include/mdk_hip.h md_text_*): Calls and Cytosines; Reads has a select and checks of its own ----
     def select(self, index):
         """a copy with the rows ``column[index]`` of every column (a boolean mask, an index tensor, a slice), same contigs and options:
         what ``render`` and ``write`` take just as they take the session's own result"""
@@ -788,14 +795,23 @@ class _Columns:
                 raise MdkError(f"text is made on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
             if t.device != dev or t.dtype != getattr(torch, dt) or not t.is_contiguous() or t.shape[0] != cols[0].shape[0]:
                 raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        L = self._renderer(dev)
+        view = md_text_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
+        return self._text_iter(L, view, dev, fmt, context, self._block_rows(block_rows))         # (checked before a file is opened; made block by block)
+
+    @staticmethod
+    def _block_rows(block_rows):
         block_rows = int(block_rows or os.environ.get("MDK_TEXT_BLOCK_ROWS") or TEXT_BLOCK_ROWS)        # (the variable is a test hook)
         if not 1 <= block_rows <= 1 << 30:
             raise MdkError("block_rows must be between 1 and 2^30")
+        return block_rows
+
+    def _renderer(self, dev):
+        """libmdk_hip.so, and this object's md_text on the columns' device made if it is not there yet"""
         L = _text_lib()
         if getattr(self, "_text", None) is None:
             self._text = _TextRenderer(L, dev.index or 0, self.contigs)
-        view = md_text_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
-        return self._text_iter(L, view, dev, fmt, context, block_rows)         # (checked before a file is opened; made block by block)
+        return L
 
     def _text_iter(self, L, view, dev, fmt, context, block_rows):
         import torch
@@ -804,7 +820,9 @@ class _Columns:
             r1 = min(n, r0 + block_rows)
             torch.cuda.current_stream(dev).synchronize()         # the columns are complete, and nothing of torch's is queued on memory it hands out next
             size = C.c_int64()
-            if fmt == TEXT_CYTOSINE_REPORT:
+            if fmt == TEXT_PERREAD:
+                rc = L.md_text_measure_reads(self._text.h, C.byref(view), int(self.name_bytes.shape[0]), r0, r1, C.byref(size))
+            elif fmt == TEXT_CYTOSINE_REPORT:
                 rc = L.md_text_measure_cytosines(self._text.h, C.byref(view), r0, r1, -1 if context is None else int(context), C.byref(size))
             else:
                 rc = L.md_text_measure_calls(self._text.h, C.byref(view), r0, r1, fmt, -1 if context is None else int(context), C.byref(size))
@@ -916,6 +934,86 @@ class Reads(_Columns):
     def _sizes(cls, L, out, n):
         return {"name_offsets": n + 1, "name_bytes": int(L.mdk_reads_name_bytes(out))}
 
+    def _checked(self):
+        """the columns, after the checks of the ragged layout: one entry per row, ``len + 1`` offsets, all on one device"""
+        import torch
+        cols = [getattr(self, name) for name, _ in self.COLUMNS]
+        dev, n = cols[0].device, len(self)
+        for t, (name, dt) in zip(cols, self.COLUMNS):
+            want = n + 1 if name == "name_offsets" else None if name == "name_bytes" else n
+            if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or (want is not None and t.shape[0] != want):
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev}" + ("" if want is None else " with len + 1 entries" if want == n + 1 else " with one entry per row"))
+        return cols, dev
+
+    def _text_blocks(self, fmt, context, block_rows):
+        cols, dev = self._checked()
+        if dev.type != "cuda":
+            raise MdkError(f"text is made on the device: the columns are {dev.type} tensors, and there is no CPU path")
+        L = self._renderer(dev)
+        view = md_reads_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
+        return self._text_iter(L, view, dev, TEXT_PERREAD, None, self._block_rows(block_rows))
+
+    def render(self, block_rows=None):
+        """The bytes of the file `perRead -o` writes (no header: the command prints none), as a uint8 tensor on the columns' device, made
+        there (k_rtext_len / k_rtext_fill, csrc/mdk_text.hip) from whatever the columns hold now: one line per row, covered or not.  A contig
+        index outside ``contigs``, offsets that decrease or leave ``name_bytes``, and a name longer than 255 bytes raise MdkError; so do
+        CPU tensors: there is no CPU path."""
+        return self._render(TEXT_PERREAD, None, b"", block_rows)
+
+    def write(self, path, block_rows=None):
+        """The file `perRead -o path` writes (``path`` is the file's name, not a prefix, as the command's -o is); blocks as ``Calls.write``.
+        No rows give an empty file.  Returns the path."""
+        return self._write_file(os.fspath(path), TEXT_PERREAD, None, b"", block_rows)
+
+    def select(self, index):
+        """a copy with the rows ``index`` names -- a boolean mask, an int64 index tensor (any order, repeats allowed) or a slice --, same
+        contigs: the per-row columns indexed with torch, ``name_offsets`` the scan of the selected names' lengths, ``name_bytes`` re-packed
+        (on the device by k_rtext_gather, a workgroup per 256 names; on CPU tensors with torch)"""
+        import copy
+        import torch
+        cols, dev = self._checked()
+        n = len(self)
+        if isinstance(index, slice):
+            idx = torch.arange(*index.indices(n), device=dev)          # (a negative step too, which torch's own indexing refuses)
+        else:
+            index = torch.as_tensor(index, device=dev)
+            if index.dtype == torch.bool:
+                if index.shape != (n,):
+                    raise MdkError("a mask must have one entry per row")
+                idx = index.nonzero().reshape(-1)
+            elif index.dtype == torch.int64 and index.dim() == 1:
+                idx = torch.where(index < 0, index + n, index)
+                if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+                    raise MdkError("an index is not a row")
+            else:
+                raise MdkError("select takes a boolean mask, an int64 index tensor or a slice")
+        idx = idx.contiguous()
+        c = copy.copy(self)
+        c._text = None
+        for name in ("contig", "pos", "nmeth", "nunmeth"):
+            setattr(c, name, getattr(self, name)[idx].contiguous())
+        off = self.name_offsets
+        lens = off[idx + 1] - off[idx]
+        new_off = torch.zeros(idx.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens, 0, out=new_off[1:])
+        total = int(new_off[-1]) if idx.numel() else 0
+        if total < 0 or (idx.numel() and int(lens.min()) < 0):
+            raise MdkError("the name offsets decrease")
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        if dev.type != "cuda":
+            if total:          # byte k of the result lies lens-scan[k's row] past its row's start in the source
+                row = torch.repeat_interleave(torch.arange(idx.numel()), lens)
+                out = self.name_bytes[off[idx][row] + (torch.arange(total) - new_off[:-1][row])].contiguous()
+        elif idx.numel():
+            L = self._renderer(dev)
+            torch.cuda.current_stream(dev).synchronize()
+            rc = L.md_text_gather_names(self._text.h, C.c_void_p(off.data_ptr()), C.c_void_p(self.name_bytes.data_ptr()), n, int(self.name_bytes.shape[0]),
+                                        C.c_void_p(idx.data_ptr()), idx.numel(), C.c_void_p(new_off.data_ptr()), C.c_void_p(out.data_ptr()), total)
+            if rc:
+                raise _rc_error("md_text_gather_names", rc, L.md_dev_last_error().decode())
+        c.name_offsets, c.name_bytes = new_off, out
+        return c
+
     def names(self):
         """the read names on the host, as str"""
         off, b = self.name_offsets.cpu().tolist(), self.name_bytes.cpu().numpy().tobytes()
@@ -960,6 +1058,18 @@ class Bias(_Columns):
     def options(self):
         """the suggestion as argv tokens, ["--OT", "a,b,c,d", "--OB", ...]: ready to append to an extract command line"""
         return [t for k, v in self.suggested.items() for t in ("--" + k, ",".join(str(x) for x in v))]
+
+    def render(self):
+        """The `mbias --txt` table as the command prints it (csrc/host/mdk_mbias.c mdk_mbias_report), as bytes: the header line, then one
+        line per row.  Made on the host from the row columns, CPU tensors or device ones: the table has at most 8 x read length rows, so
+        a kernel would be complexity without a payoff."""
+        return ("Strand\tRead\tPosition\tnMethylated\tnUnmethylated\n" + "".join("%s\t%i\t%i\t%u\t%u\n" % r for r in self.rows())).encode()
+
+    def write(self, path):
+        """``render()`` into the file ``path``; returns the path"""
+        with open(path, "wb") as f:
+            f.write(self.render())
+        return path
 
     def rows(self):
         """(strand name, read, position, nmeth, nunmeth) tuples on the host: the lines of the --txt table"""

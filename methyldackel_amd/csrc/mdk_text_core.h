@@ -1,12 +1,13 @@
 // mdk_text_core.h -- the text of `extract`'s output lines, made without printf: what csrc/host/mdk_emit.c put_site writes for a row, byte for
 // byte, from integer arithmetic alone.
 //
-// Five formats (the layouts of put_site):
+// Six formats (the layouts of put_site, and of perRead's addRead as csrc/host/mdk_cmd_perread.c writes it):
 //   MD_TEXT_BEDGRAPH         chrom \t start \t end \t (int)(100.0 * m / cov) \t m \t u \n
 //   MD_TEXT_FRACTION         chrom \t start \t end \t %f of m / cov \n
 //   MD_TEXT_COUNTS           chrom \t start \t end \t cov \n
 //   MD_TEXT_METHYLKIT        chrom . start+1 \t chrom \t start+1 \t F|R \t cov \t %6.2f of 100 m / cov \t %6.2f of 100 u / cov \n
 //   MD_TEXT_CYTOSINE_REPORT  chrom \t pos \t +|- \t m \t u \t C G|HG|HH \t trinucleotide \n
+//   MD_TEXT_PERREAD          name \t chrom \t pos \t %f of 100 m / cov, or the characters 0.0 when cov == 0 \t cov \n   (txt_read_*: a row is a read)
 // with cov = m + u in uint32, as the host adds them.  --logit is not here: its value is log(f) - log(1 - f), and neither glibc's log nor the
 // device library's is correctly rounded, so the same bytes cannot be promised.
 //
@@ -31,9 +32,9 @@
 
 #ifndef MD_TEXT_FORMATS               // (include/mdk_hip.h declares the same)
 #define MD_TEXT_FORMATS
-enum { MD_TEXT_BEDGRAPH = 0, MD_TEXT_FRACTION, MD_TEXT_COUNTS, MD_TEXT_METHYLKIT, MD_TEXT_CYTOSINE_REPORT, MD_TEXT_N_FORMATS };
+enum { MD_TEXT_BEDGRAPH = 0, MD_TEXT_FRACTION, MD_TEXT_COUNTS, MD_TEXT_METHYLKIT, MD_TEXT_CYTOSINE_REPORT, MD_TEXT_PERREAD, MD_TEXT_N_FORMATS };
 #endif
-#define MD_TEXT_NAME_MAX 255           // bytes of a contig name a renderer takes
+#define MD_TEXT_NAME_MAX 255           // bytes of a contig name a renderer takes, and of a read name
 
 // ---- integers: what printf's %u / %i write (put_u32 / put_i32 of mdk_emit.c) ----
 MDK_TXT int txt_digits_u64(uint64_t v) { int n = 1; while(v >= 10) { v /= 10; n++; } return n; }
@@ -147,6 +148,45 @@ MDK_TXT char *txt_put_line(char *q, int fmt, const uint8_t *name, uint32_t name_
     *q++ = '\n';
     return q;
 }
+// ---- a perRead line: every row has one, covered or not (addRead prints the read whatever it counted) ----
+// what follows the read name: \t chrom \t pos \t V \t cov \n with cov = m + u in uint32, V = %f of 100. * ((double)m) / cov, or 0.0 without coverage
+MDK_TXT uint32_t txt_read_tail_len(uint32_t contig_len, int32_t pos, uint32_t m, uint32_t u) {
+    const uint32_t cov = m + u;
+    return 1 + contig_len + 1 + txt_digits_i32(pos) + 1 + (cov ? (uint32_t)txt_fixed_len(txt_percent(m, cov), 6, 0) : 3u) + 1 + txt_digits_u32(cov) + 1;
+}
+MDK_TXT uint32_t txt_read_line_len(uint32_t name_len, uint32_t contig_len, int32_t pos, uint32_t m, uint32_t u) { return name_len + txt_read_tail_len(contig_len, pos, m, u); }
+MDK_TXT char *txt_put_read_tail(char *q, const uint8_t *contig, uint32_t contig_len, int32_t pos, uint32_t m, uint32_t u) {
+    const uint32_t cov = m + u;
+    *q++ = '\t'; q = txt_put_name(q, contig, contig_len); *q++ = '\t'; q = txt_put_i32(q, pos); *q++ = '\t';
+    if(cov) q = txt_put_fixed(q, txt_percent(m, cov), 6, 0); else { *q++ = '0'; *q++ = '.'; *q++ = '0'; }
+    *q++ = '\t'; q = txt_put_u32(q, cov); *q++ = '\n';
+    return q;
+}
+// the whole line at q (txt_read_line_len bytes), the name a byte at a time; returns its end
+MDK_TXT char *txt_put_read_line(char *q, const uint8_t *name, uint32_t name_len, const uint8_t *contig, uint32_t contig_len, int32_t pos, uint32_t m, uint32_t u) {
+    return txt_put_read_tail(txt_put_name(q, name, name_len), contig, contig_len, pos, m, u);
+}
+// n bytes from buf[s ..) to dst, four at a time (k_rtext_fill: a read name from the staged span in LDS into the image): whole 4-byte
+// ALIGNED words of dst, each made of the two aligned words of buf that hold its bytes; the bytes before the first and after the last whole
+// word singly.  buf is 4-byte aligned and readable up to the aligned word after the one holding byte s + n - 1 (its value is not used).
+MDK_TXT uint32_t txt_word(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, __builtin_assume_aligned(p, 4), 4); return v; }
+MDK_TXT void txt_copy_words(uint8_t *dst, const uint8_t *buf, uint32_t s, uint32_t n) {
+    uint32_t i = 0;
+    while(i < n && ((uintptr_t)(dst + i) & 3u)) { dst[i] = buf[s + i]; i++; }
+    if(i + 4 <= n) {
+        const uint32_t sh = 8u * ((s + i) & 3u);
+        const uint8_t *w = buf + ((s + i) & ~3u);
+        uint32_t lo = txt_word(w);
+        for(; i + 4 <= n; i += 4) {
+            w += 4;
+            const uint32_t hi = txt_word(w), v = sh ? (lo >> sh) | (hi << (32u - sh)) : lo;       // (little endian: byte k of a word is bits 8k..8k+7)
+            __builtin_memcpy(__builtin_assume_aligned(dst + i, 4), &v, 4);
+            lo = hi;
+        }
+    }
+    for(; i < n; i++) dst[i] = buf[s + i];
+}
+
 // ---- a workgroup's lines, assembled in an image and streamed out as aligned 16-byte quads (k_text_fill; tools/text_emu --emulate) ----
 // The image holds the workgroup's `total` bytes from offset sh = (destination address) mod 16 on, so image quad k is the ALIGNED destination
 // quad k counted from (destination - sh).  Quads [quad0, quad1) lie wholly inside the workgroup's text and go out whole; image bytes
