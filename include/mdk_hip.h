@@ -515,6 +515,26 @@ int  md_text_gather_names(md_text *t, const int64_t *src_off, const uint8_t *src
                           const int64_t *index, int64_t n, const int64_t *dst_off, uint8_t *dst_bytes, int64_t n_dst_bytes);
 void md_text_close(md_text *t);
 
+/* ---- mergeContext on the device: per-strand rows folded into per-CpG / per-CHG rows (csrc/mdk_merge.hip, csrc/mdk_merge_core.h) ----
+ * What the `mergeContext` command does to the lines of a bedGraph, done to rows held as DEVICE-resident md_calls_cols -- which carry the
+ * context and the strand the command looks up in the FASTA.  The n rows must be strictly ascending in (contig, start), each one cytosine:
+ * end == start + 1, strand +1 (a C) or -1 (a G), context 0 / 1 / 2.  With d = context + 1:
+ *   context 2             the row as it is, strand kept;
+ *   context < 2, a C at p (contig, p, p + d + 1, its counts plus those of the next row if that is the G of the same contig and context at p + d,
+ *                         context, strand 0), at the C's place;
+ *   context < 2, a G at q no row if the row before it is its C; otherwise (contig, q - d, q + 1, its counts, context, 0);
+ * and a row whose nmeth + nunmeth < min_depth is dropped (min_depth 0: none is).  Two steps on a renderer (its stream, its table of one entry
+ * per 256 rows, its contig count; the same rules: synchronous, one thread at a time, the columns complete when the call is made):
+ *   md_text_merge_measure  *rows = the number of rows of the result.  n at most 2^30.  MDK_ERR_ARG, with md_dev_last_error naming it, for a
+ *                          CpG / CHG row with strand 0 or a row with end != start + 1 (merged already), a context above 2, a contig index
+ *                          outside the name table, rows not strictly ascending, a G without its C at q < d, counts that add up to more than
+ *                          INT32_MAX.  A measure of either kind voids the renderer's earlier one: there is one table;
+ *   md_text_merge_fill     the seven columns of the result into `dst`, DEVICE memory of the caller of exactly *rows entries each, apart from
+ *                          the measured columns.  Columns that changed since the measure are detected per workgroup and end the call with
+ *                          MDK_ERR_ARG; nothing is written past dst. */
+int  md_text_merge_measure(md_text *t, const md_calls_cols *cols, int64_t n, int32_t min_depth, int64_t *rows);
+int  md_text_merge_fill(md_text *t, const md_calls_cols *dst, int64_t rows);
+
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
  * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram, the calls and reads state
  * are dropped, every slot's buffers are given back.  Pointers the library returned for the handle before (md_sites, md_sites_dev,

@@ -179,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close"]
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
@@ -696,6 +696,8 @@ def _text_lib():
         L.md_text_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.md_text_gather_names.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
         L.md_text_close.argtypes = [C.c_void_p]; L.md_text_close.restype = None
+        L.md_text_merge_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.md_text_merge_fill.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
         L._text_types = True
     return L
 
@@ -813,6 +815,31 @@ class _Columns:
             self._text = _TextRenderer(L, dev.index or 0, self.contigs)
         return L
 
+    def _merged(self, cols, min_depth):
+        """mergeContext over ``cols`` -- this object's rows as the seven tensors of CALL_COLUMNS -- on their device (k_merge_len /
+        k_merge_fill, csrc/mdk_merge.hip): a Calls of new tensors, allocated by torch at the measured row count"""
+        import torch
+        min_depth = int(min_depth)
+        if min_depth < 0:
+            raise MdkError("min_depth must not be negative")
+        dev, n = cols[0].device, int(cols[0].shape[0])
+        for t, (name, dt) in zip(cols, CALL_COLUMNS):
+            if t.device.type != "cuda":
+                raise MdkError(f"rows are merged on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+            if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        L = self._renderer(dev)
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        view, rows = md_text_cols(*[C.c_void_p(t.data_ptr()) for t in cols]), C.c_int64()
+        rc = L.md_text_merge_measure(self._text.h, C.byref(view), n, min_depth, C.byref(rows))
+        if rc:
+            raise _rc_error("md_text_merge_measure", rc, L.md_dev_last_error().decode())
+        out = {name: torch.empty(rows.value, dtype=getattr(torch, dt), device=dev) for name, dt in CALL_COLUMNS}
+        rc = L.md_text_merge_fill(self._text.h, C.byref(md_text_cols(*[C.c_void_p(out[name].data_ptr()) for name, _ in CALL_COLUMNS])), rows.value)
+        if rc:
+            raise _rc_error("md_text_merge_fill", rc, L.md_dev_last_error().decode())
+        return Calls(self.contigs, out, merged=True, contexts_on=self.contexts_on)
+
     def _text_iter(self, L, view, dev, fmt, context, block_rows):
         import torch
         n = len(self)
@@ -915,6 +942,24 @@ class Calls(_Columns):
         code = self._format(fmt)
         return [self._write_file(os.path.join(directory, f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}") if directory is not None else f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}",
                                  code, k, self.header(fmt, k, prefix), block_rows) for k in self.contexts_on]
+
+    def merge_context(self, min_depth=1):
+        """The rows the `mergeContext` command makes of these: a new Calls (``merged`` true, same ``contigs`` and ``contexts_on``, new tensors
+        on this one's device) in which a CpG's or CHG's C and G are ONE row -- ``start`` the C, ``end`` one past the G, the counts added,
+        ``strand`` 0 --, a C or G whose partner is no row is that row alone, and CHH rows are as they were.  Rows whose nmeth + nunmeth is
+        below ``min_depth`` are then dropped (CHH rows too, as `extract -d` does; 0 keeps every row).  Made on the device from the columns
+        alone (csrc/mdk_merge.hip): ``context`` and ``strand`` are what the command looks up in the FASTA.  The rows must be strictly
+        ascending in (contig, start), as a session returns them and as ``select`` with a mask or an ascending index keeps them; rows in
+        another order, rows merged already, a context above 2, a contig index outside ``contigs``, a G without its C closer to the
+        contig's start than its site is long, and counts adding up past 2^31 - 1 raise MdkError (rc -3); so do CPU tensors: there is no
+        CPU path.  One `extract` run at -d 1 thus gives the per-strand tables, the merged ones at any depth, and the files of both.
+        What always holds, at the default ``min_depth``: ``m.write(p)`` is, after the header line, what `MethylDackel mergeContext` prints for the file ``self.write``
+        made.  It equals `extract --mergeContext [-d D]` (``min_depth=D``) too, for runs without the variant filter (--minOppositeDepth)
+        and without -l: under the first the command zeroes a C's counts when its G is a variant, under the second its pending sites
+        never cross a chunk, and rows made afterwards cannot know either."""
+        if self.merged:
+            raise MdkError("merge_context: these rows are merged already (merged is true)")
+        return self._merged([getattr(self, name) for name, _ in CALL_COLUMNS], min_depth)
 
     def rows(self, context=None):
         """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
@@ -1109,6 +1154,14 @@ class Cytosines(_Columns):
         """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  Returns the path."""
         name = f"{prefix}.cytosine_report.txt"
         return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows)
+
+    def merge_context(self):
+        """The report per CpG / CHG site: a Calls (``merged`` true) with a row for every CpG and CHG site and every CHH cytosine of the
+        reference, covered or not -- ``Calls.merge_context`` at ``min_depth=0`` over a view of these columns (``start`` = pos - 1, ``end`` =
+        pos; counts, contig, context and strand are not copied).  Which rows there are depends on the reference and the schedule alone,
+        so two samples' results line up row for row: ``torch.stack([a.merge_context().nmeth, b.merge_context().nmeth])`` is the samples x
+        CpGs matrix.  ``Calls.render`` prints no line for an uncovered row."""
+        return self._merged([self.contig, self.pos - 1, self.pos, self.nmeth, self.nunmeth, self.context, self.strand], 0)
 
     def rows(self):
         """(chrom, pos, "+"/"-", nmeth, nunmeth, "CG"/"CHG"/"CHH", trinucleotide) tuples on the host: the seven fields of a line"""

@@ -28,47 +28,20 @@
 //                  image and streamed out in the same way
 // k_text_fill re-checks every workgroup's total against what k_text_len recorded: columns that changed between the two calls end the fill
 // with an error instead of a write past the buffer.
-#include "mdk_hip_internal.hpp"
+// The handle, the argument blocks and the scan of the block table are in mdk_text_internal.hpp: mdk_merge.hip (mergeContext over rows) works
+// on the same handle.
+#include "mdk_text_internal.hpp"
 #include "mdk_text_core.h"
 #include <string>
 
-#define TEXT_WG 256
-#define TEXT_SCAN_WG 1024
 #define TEXT_LDS_BYTES (24 * 1024)        // the image: 96 bytes per row (a default bedGraph line of a human contig is ~35, a methylKit one ~55)
-#define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
 #define READS_IMG_BYTES (30 * 1024)       // the reads image: 120 bytes per row (an 80-byte name, a 5-byte contig name and the longest digits: 120)
 #define READS_STAGE_BYTES (22 * 1024)     // the staged names: 88 bytes per row.  With the image 53,312 bytes of LDS: three workgroups in a CU's 160 KiB
 enum { TEXT_E_CONTIG = 1, TEXT_E_STRAND0 = 2, TEXT_E_CONTEXT = 4, TEXT_E_CHANGED = 8, TEXT_E_OFFSET = 16, TEXT_E_DECREASING = 32, TEXT_E_NAME = 64, TEXT_E_INDEX = 128, TEXT_E_DST = 256 };
 
-struct TextStatus { int64_t total; uint32_t err, pad; };
-// the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
-struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
-struct KText {
-    TextView v; int64_t r0; uint32_t n; int32_t fmt, context, n_contigs;
-    const uint32_t *name_off; const uint8_t *names;          // name c = names[name_off[c] .. name_off[c + 1])
-    uint32_t *btot; int64_t *boff; TextStatus *st;
-    uint8_t *dst; int64_t bytes;
-};
-
-// the Reads layout: name i = name_bytes[name_off[i] .. name_off[i + 1]), offsets into n_name_bytes bytes
-struct KReads {
-    const int32_t *contig, *pos, *m, *u; const int64_t *name_off; const uint8_t *name_bytes; int64_t n_name_bytes;
-    int64_t r0; uint32_t n; int32_t n_contigs;
-    const uint32_t *cname_off; const uint8_t *cnames;         // the renderer's contig names
-    uint32_t *btot; int64_t *boff; TextStatus *st;
-    uint8_t *dst; int64_t bytes;
-};
 struct KGather {
     const int64_t *src_off; const uint8_t *src_bytes; int64_t n_src, n_src_bytes;
     const int64_t *index; uint32_t n; const int64_t *dst_off; uint8_t *dst; int64_t n_dst_bytes; TextStatus *st;
-};
-
-struct md_text {
-    int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
-    uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
-    uint32_t *d_btot = nullptr; int64_t *d_boff = nullptr; size_t cap_blocks = 0;
-    TextStatus *d_st = nullptr, *h_st = nullptr;
-    KText K; KReads R; bool measured = false, reads = false;          // reads: the range measured last is one of md_text_measure_reads
 };
 
 // row i of the range: the length of its line (0: no line) and what txt_put_line needs
@@ -100,17 +73,7 @@ __global__ __launch_bounds__(TEXT_WG) void k_text_len(const KText K) {
 
 __global__ __launch_bounds__(TEXT_SCAN_WG) void k_text_blocks(const KText K) {
     __shared__ int64_t wtot[TEXT_SCAN_WG / 64];
-    const uint32_t nb = (K.n + TEXT_WG - 1) / TEXT_WG;
-    int64_t carry = 0;
-    for(uint32_t b0 = 0; b0 < nb; b0 += TEXT_SCAN_WG) {          // (uniform trip count: every thread takes part in every scan)
-        const uint32_t b = b0 + threadIdx.x;
-        const int64_t v = b < nb ? (int64_t)K.btot[b] : 0;
-        int64_t total;
-        const int64_t ex = block_excl_scan<TEXT_SCAN_WG>(v, wtot, total);
-        if(b < nb) K.boff[b] = carry + ex;
-        carry += total;
-    }
-    if(threadIdx.x == 0) K.st->total = carry;
+    text_scan_blocks(K.btot, K.boff, K.st, (K.n + TEXT_WG - 1) / TEXT_WG, wtot);
 }
 
 // a workgroup's image out to g (img[P.sh + i] is g[i]): the whole quads as 16-byte stores, consecutive lanes consecutive quads; the bytes that
@@ -300,8 +263,7 @@ static int text_status(md_text *t, const char *what) {
     return MDK_ERR_ARG;
 }
 
-// the block table for nb workgroups
-static int text_blocks_reserve(md_text *t, uint32_t nb) {
+int text_blocks_reserve(md_text *t, uint32_t nb) {
     if(nb > t->cap_blocks) {
         (void)hipFree(t->d_btot); (void)hipFree(t->d_boff); t->d_btot = nullptr; t->d_boff = nullptr; t->cap_blocks = 0;
         const size_t want = (size_t)nb + nb / 4 + 64;
@@ -315,7 +277,7 @@ static int text_blocks_reserve(md_text *t, uint32_t nb) {
 
 static int text_measure(md_text *t, const TextView &v, int64_t r0, int64_t r1, int fmt, int context, int64_t *bytes, const char *what) {
     if(!t || !bytes || r0 < 0 || r1 < r0 || r1 - r0 > TEXT_MAX_ROWS || context < -1 || context > 2) return fail(MDK_ERR_ARG, what, hipSuccess);
-    *bytes = 0; t->measured = false;
+    *bytes = 0; t->measured = false; t->merge_measured = false;
     const uint32_t n = (uint32_t)(r1 - r0), nb = (n + TEXT_WG - 1) / TEXT_WG;
     if(n && (!v.contig || !v.a || !v.m || !v.u || !v.ctx || !v.strand || (fmt == MD_TEXT_CYTOSINE_REPORT ? !v.tri : !v.b))) return fail(MDK_ERR_ARG, what, hipSuccess);
     HIPCHK(hipSetDevice(t->device));
@@ -338,7 +300,7 @@ static int text_measure(md_text *t, const TextView &v, int64_t r0, int64_t r1, i
 extern "C" int md_text_measure_reads(md_text *t, const md_reads_cols *c, int64_t n_name_bytes, int64_t r0, int64_t r1, int64_t *bytes) {
     const char *const what = "md_text_measure_reads";
     if(!t || !c || !bytes || n_name_bytes < 0 || r0 < 0 || r1 < r0 || r1 - r0 > TEXT_MAX_ROWS) return fail(MDK_ERR_ARG, what, hipSuccess);
-    *bytes = 0; t->measured = false;
+    *bytes = 0; t->measured = false; t->merge_measured = false;
     const uint32_t n = (uint32_t)(r1 - r0), nb = (n + TEXT_WG - 1) / TEXT_WG;
     if(n && (!c->contig || !c->pos || !c->nmeth || !c->nunmeth || !c->name_off || (n_name_bytes && !c->name_bytes))) return fail(MDK_ERR_ARG, what, hipSuccess);
     HIPCHK(hipSetDevice(t->device));

@@ -1,0 +1,64 @@
+// mdk_text_internal.hpp -- what the two sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows): the
+// handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
+// scan of the block table.
+#ifndef MDK_TEXT_INTERNAL_HPP
+#define MDK_TEXT_INTERNAL_HPP
+#include "mdk_hip_internal.hpp"
+
+#define TEXT_WG 256
+#define TEXT_SCAN_WG 1024
+#define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
+
+struct TextStatus { int64_t total; uint32_t err, pad; };
+// the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
+struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
+struct KText {
+    TextView v; int64_t r0; uint32_t n; int32_t fmt, context, n_contigs;
+    const uint32_t *name_off; const uint8_t *names;          // name c = names[name_off[c] .. name_off[c + 1])
+    uint32_t *btot; int64_t *boff; TextStatus *st;
+    uint8_t *dst; int64_t bytes;
+};
+
+// the Reads layout: name i = name_bytes[name_off[i] .. name_off[i + 1]), offsets into n_name_bytes bytes
+struct KReads {
+    const int32_t *contig, *pos, *m, *u; const int64_t *name_off; const uint8_t *name_bytes; int64_t n_name_bytes;
+    int64_t r0; uint32_t n; int32_t n_contigs;
+    const uint32_t *cname_off; const uint8_t *cnames;         // the renderer's contig names
+    uint32_t *btot; int64_t *boff; TextStatus *st;
+    uint8_t *dst; int64_t bytes;
+};
+
+// mergeContext over rows (mdk_merge.hip): the measured columns, and where the fill writes
+struct KMerge {
+    const int32_t *contig, *start, *end, *m, *u; const uint8_t *ctx; const int8_t *strand;
+    uint32_t n; int32_t n_contigs, min_depth;
+    uint32_t *btot; int64_t *boff; TextStatus *st;
+    md_calls_cols dst; int64_t rows;
+};
+
+struct md_text {
+    int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
+    uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
+    uint32_t *d_btot = nullptr; int64_t *d_boff = nullptr; size_t cap_blocks = 0;
+    TextStatus *d_st = nullptr, *h_st = nullptr;
+    KText K; KReads R; bool measured = false, reads = false;          // reads: the range measured last is one of md_text_measure_reads
+    KMerge M; bool merge_measured = false;                            // the block table holds md_text_merge_measure's totals (one table: a measure of either kind voids the other's)
+};
+
+// the block table for nb workgroups
+MDK_HIDDEN int text_blocks_reserve(md_text *t, uint32_t nb);
+
+// one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
+__device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
+    int64_t carry = 0;
+    for(uint32_t b0 = 0; b0 < nb; b0 += TEXT_SCAN_WG) {          // (uniform trip count: every thread takes part in every scan)
+        const uint32_t b = b0 + threadIdx.x;
+        const int64_t v = b < nb ? (int64_t)btot[b] : 0;
+        int64_t total;
+        const int64_t ex = block_excl_scan<TEXT_SCAN_WG>(v, wtot, total);
+        if(b < nb) boff[b] = carry + ex;
+        carry += total;
+    }
+    if(threadIdx.x == 0) st->total = carry;
+}
+#endif
