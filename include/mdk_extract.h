@@ -242,6 +242,18 @@ int  mdk_cytosines_contexts(const mdk_cytosines *c);      /* as mdk_calls_contex
 int  mdk_cytosines_copy(const mdk_cytosines *c, int column, void *dst, int to_host);
 void mdk_cytosines_free(mdk_cytosines *c);
 
+/* ---- the reference genome for callers that parse text (include/mdk_hip.h md_text_reference): the FASTA reader every command uses ----
+ * mdk_reference_load reads the whole file (names cut at the first blank, the printable characters of the sequence lines, case kept) and
+ * returns 0 and *out, or -1 and NULL.  Names and bases belong to the object until mdk_reference_free; mdk_reference_bases is
+ * mdk_reference_length bytes without a terminator.  An index outside [0, n_contigs) gives NULL / -1. */
+typedef struct mdk_reference mdk_reference;
+int  mdk_reference_load(const char *fasta, mdk_reference **out);
+int  mdk_reference_n_contigs(const mdk_reference *r);
+const char *mdk_reference_name(const mdk_reference *r, int i);
+int64_t mdk_reference_length(const mdk_reference *r, int i);
+const char *mdk_reference_bases(const mdk_reference *r, int i);
+void mdk_reference_free(mdk_reference *r);
+
 /* ---- `mergeContext` (mergeContext.c; main.c:19,53-54): text-to-text host tool, no device work ---- */
 int  mergeContext_main(int argc, char *argv[]);
 

@@ -535,6 +535,42 @@ void md_text_close(md_text *t);
 int  md_text_merge_measure(md_text *t, const md_calls_cols *cols, int64_t n, int32_t min_depth, int64_t *rows);
 int  md_text_merge_fill(md_text *t, const md_calls_cols *dst, int64_t rows);
 
+/* ---- text read back into columns: a bedGraph or a cytosine report parsed on the device (csrc/mdk_parse.hip, csrc/mdk_parse_core.h) ----
+ * The way back from md_text_fill: `bytes` bytes of text in DEVICE memory become rows in the layouts above, without the host looking at a line.
+ * A line starts at byte 0 and after every '\n' and ends before the next '\n' or at the end of the text; one '\r' before the '\n' is dropped; a
+ * line that begins with `track` is skipped wherever it stands; every other line is a row.  A line is at most 512 bytes, its '\n' included.
+ *   MD_PARSE_BEDGRAPH         chrom start end pct nmeth nunmeth, six fields separated by single tabs, into md_calls_cols.  chrom is looked up
+ *                             in the renderer's names (a binary search per line; of equal names the first), the four numbers are 1 to 10 decimal
+ *                             digits at most INT32_MAX, pct is not looked at.  end must be start + 1: per-cytosine files only.  The strand
+ *                             (+1 a C, -1 a G) and the context (0 CpG, 1 CHG, 2 CHH) come from the contig's bases around start, by the rule of
+ *                             the `mergeContext` command and of a session's own classification, so the contig must be resident:
+ *   md_text_reference         copies the `len` bases of contig `contig` from HOST memory to the renderer's device, where they stay until they
+ *                             are replaced, dropped (bases = NULL) or the renderer is closed.  Synchronous.  Case as in the FASTA.
+ *   MD_PARSE_CYTOSINE_REPORT  chrom pos +|- nmeth nunmeth CG|CHG|CHH tri, seven fields, into md_cytosines_cols; pos stays 1-based and is at
+ *                             least 1, tri is three letters of ACGTN.  No reference is needed.
+ * Stricter than the command on purpose: signs, blanks, doubled tabs, trailing columns and numbers past INT32_MAX, which its strtoll / strtok
+ * take, are refused.  What is accepted gives, after md_text_merge_*, what the command prints for the file.  Two steps, with the rules of this
+ * section -- synchronous on the renderer's stream, one thread at a time, the text complete when the call is made, a measure of any kind voids
+ * the renderer's earlier one:
+ *   md_text_parse_measure     *rows = the number of rows.  `text` is 16-byte aligned device memory, bytes at most 2^31 - 1.  Nothing is
+ *                             validated yet;
+ *   md_text_parse_fill_*      the seven columns into `dst`, DEVICE memory of exactly *rows entries each (3 * rows bytes of trinucleotide), the
+ *                             one that matches the measured format.  Every line is validated here: MDK_ERR_ARG, with md_dev_last_error naming
+ *                             the refusal of the offending line that starts earliest -- an empty line, too few / too many / empty fields, a
+ *                             non-digit, an overflow, an unknown contig, end != start + 1, a position outside the contig, a base that is neither
+ *                             C nor G, a bad strand / context / trinucleotide, a line longer than 512 bytes, a contig without resident bases --
+ *                             and md_text_parse_error_offset giving that line's first byte (-1: none, or the text changed since the measure,
+ *                             which is detected per 4096 bytes).  The contents of dst are unspecified then; nothing is written past dst. */
+#ifndef MD_PARSE_FORMATS
+#define MD_PARSE_FORMATS
+enum { MD_PARSE_BEDGRAPH = 0, MD_PARSE_CYTOSINE_REPORT = 1 };
+#endif
+int  md_text_reference(md_text *t, int32_t contig, const char *bases, int64_t len);
+int  md_text_parse_measure(md_text *t, const uint8_t *text, int64_t bytes, int fmt, int64_t *rows);
+int  md_text_parse_fill_calls(md_text *t, const md_calls_cols *dst, int64_t rows);
+int  md_text_parse_fill_cytosines(md_text *t, const md_cytosines_cols *dst, int64_t rows);
+int64_t md_text_parse_error_offset(const md_text *t);
+
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
  * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram, the calls and reads state
  * are dropped, every slot's buffers are given back.  Pointers the library returned for the handle before (md_sites, md_sites_dev,

@@ -179,7 +179,8 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill"]
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill",
+               "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
@@ -189,7 +190,8 @@ EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_
                    "mdk_session_open", "mdk_session_extract", "mdk_session_close", "mdk_calls_count", "mdk_calls_n_contigs", "mdk_calls_contig_name", "mdk_calls_merged", "mdk_calls_contexts", "mdk_calls_copy", "mdk_calls_free",
                    "mdk_session_perread", "mdk_reads_count", "mdk_reads_name_bytes", "mdk_reads_n_contigs", "mdk_reads_contig_name", "mdk_reads_copy", "mdk_reads_free",
                    "mdk_mbias_suggest", "mdk_session_mbias", "mdk_bias_count", "mdk_bias_len", "mdk_bias_resubmitted", "mdk_bias_suggested", "mdk_bias_copy", "mdk_bias_free",
-                   "mdk_session_cytosines", "mdk_cytosines_count", "mdk_cytosines_n_contigs", "mdk_cytosines_contig_name", "mdk_cytosines_contexts", "mdk_cytosines_copy", "mdk_cytosines_free"]
+                   "mdk_session_cytosines", "mdk_cytosines_count", "mdk_cytosines_n_contigs", "mdk_cytosines_contig_name", "mdk_cytosines_contexts", "mdk_cytosines_copy", "mdk_cytosines_free",
+                   "mdk_reference_load", "mdk_reference_n_contigs", "mdk_reference_name", "mdk_reference_length", "mdk_reference_bases", "mdk_reference_free"]
 
 _hip = None
 _ext = None
@@ -683,6 +685,8 @@ TEXT_PERREAD = 5
 TEXT_SUFFIX = (".bedGraph", ".meth.bedGraph", ".counts.bedGraph", ".methylKit")
 TEXT_WHAT = ("levels", "fractions", "counts")
 TEXT_BLOCK_ROWS = 1 << 22                                     # rows per block of `write` / `render`
+PARSE_BEDGRAPH, PARSE_CYTOSINE_REPORT = 0, 1                  # MD_PARSE_* of include/mdk_hip.h
+PARSE_BLOCK_BYTES = 256 << 20                                 # bytes of a file per piece of `read`
 
 
 def _text_lib():
@@ -698,6 +702,11 @@ def _text_lib():
         L.md_text_close.argtypes = [C.c_void_p]; L.md_text_close.restype = None
         L.md_text_merge_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.md_text_merge_fill.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
+        L.md_text_reference.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        L.md_text_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+        L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
+        L.md_text_parse_fill_cytosines.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
+        L.md_text_parse_error_offset.argtypes = [C.c_void_p]; L.md_text_parse_error_offset.restype = C.c_int64
         L._text_types = True
     return L
 
@@ -887,6 +896,187 @@ class _Columns:
         return path
 
 
+# ---- text read back into columns (include/mdk_hip.h md_text_parse_*, csrc/mdk_parse.hip): Calls.read, Cytosines.read ----
+def _reference_lib():
+    L = lib_extract()
+    if not getattr(L, "_reference_types", False):
+        L.mdk_reference_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.mdk_reference_n_contigs.argtypes = [C.c_void_p]
+        L.mdk_reference_name.argtypes = [C.c_void_p, C.c_int]; L.mdk_reference_name.restype = C.c_char_p
+        L.mdk_reference_length.argtypes = [C.c_void_p, C.c_int]; L.mdk_reference_length.restype = C.c_int64
+        L.mdk_reference_bases.argtypes = [C.c_void_p, C.c_int]; L.mdk_reference_bases.restype = C.c_void_p
+        L.mdk_reference_free.argtypes = [C.c_void_p]; L.mdk_reference_free.restype = None
+        L._reference_types = True
+    return L
+
+
+class Reference:
+    """A FASTA in host memory, read by the reader every command uses: ``contigs`` (names, file order) and ``lengths``.  What
+    ``Calls.read`` looks a bedGraph line's strand and context up in: the bases go to a device once, at the first read there, and stay with
+    this object's renderer for that device, so many files share one upload.  ``close()`` gives the host copy and the device copies back."""
+
+    def __init__(self, path):
+        self._L, self._h, self._text = _reference_lib(), C.c_void_p(), {}
+        self.path = os.fspath(path)
+        if self._L.mdk_reference_load(os.fsencode(self.path), C.byref(self._h)):
+            self._h = None
+            raise MdkError(f"cannot read the reference {self.path}")
+        n = self._L.mdk_reference_n_contigs(self._h)
+        self.contigs = [os.fsdecode(self._L.mdk_reference_name(self._h, i)) for i in range(n)]
+        self.lengths = [int(self._L.mdk_reference_length(self._h, i)) for i in range(n)]
+
+    def bases(self, i):
+        """the bases of contig ``i`` as bytes, case as in the file"""
+        if self._h is None:
+            raise MdkError("the reference is closed")
+        return C.string_at(self._L.mdk_reference_bases(self._h, i), self.lengths[i]) if self.lengths[i] else b""
+
+    def _renderer(self, device):
+        """this reference's md_text on ``device``: its names and, uploaded here at the first use, its bases"""
+        if self._h is None:
+            raise MdkError("the reference is closed")
+        device = int(device)
+        if device not in self._text:
+            L = _text_lib()
+            r = _TextRenderer(L, device, self.contigs)
+            for i, n in enumerate(self.lengths):
+                rc = L.md_text_reference(r.h, i, C.c_void_p(self._L.mdk_reference_bases(self._h, i)), n)
+                if rc:
+                    raise _rc_error("md_text_reference", rc, L.md_dev_last_error().decode())
+            self._text[device] = r
+        return self._text[device]
+
+    def close(self):
+        self._text = {}
+        if self._h is not None:
+            self._L.mdk_reference_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _parse_block_bytes(block_bytes):
+    block_bytes = int(block_bytes or os.environ.get("MDK_PARSE_BLOCK_BYTES") or PARSE_BLOCK_BYTES)        # (the variable is a test hook)
+    if not 1 <= block_bytes <= (1 << 31) - 1:
+        raise MdkError("block_bytes must be between 1 and 2^31 - 1")
+    return block_bytes
+
+
+def _parse_device(device):
+    """the torch device of a read; without a GPU an MdkError: there is no CPU path"""
+    import torch
+    if lib_hip().md_dev_count() <= 0 or not torch.cuda.is_available():
+        raise MdkError("files are parsed on the device: no device is visible, and there is no CPU path")
+    return torch.device("cuda", int(device))
+
+
+def _last_newline(view, end):
+    """the index of the last newline byte in view[:end], or -1 (searched backwards, 64 KiB at a time)"""
+    while end > 0:
+        lo = max(0, end - 65536)
+        k = bytes(view[lo:end]).rfind(b"\n")
+        if k >= 0:
+            return lo + k
+        end = lo
+    return -1
+
+
+def _parse_pieces(path, block_bytes):
+    """(pinned uint8 tensor, bytes in it, offset in the file) for every piece of the file: at most ``block_bytes`` bytes, cut after its last
+    newline or at the end of the file.  The tensor is reused: a piece is consumed before the next is asked for"""
+    import torch
+    size = os.path.getsize(path)
+    pin = torch.empty(max(1, min(block_bytes, size)), dtype=torch.uint8, pin_memory=True)
+    buf = pin.numpy()
+    view = memoryview(buf)
+    cap, keep, at = pin.numel(), 0, 0
+    with open(path, "rb", buffering=0) as f:
+        while True:
+            end, eof = keep, False
+            while end < cap:
+                got = f.readinto(view[end:cap])
+                if not got:
+                    eof = True
+                    break
+                end += got
+            if not eof and end == cap and size <= cap:
+                eof = True                                   # the whole file is in the buffer
+            if end == 0:
+                return
+            cut = end if eof else _last_newline(view, end) + 1
+            if cut == 0:
+                raise MdkError(f"{path}: a line longer than block_bytes ({block_bytes}) at byte {at}")
+            yield pin, cut, at
+            keep = end - cut
+            if keep:
+                buf[:keep] = buf[cut:end].copy()
+            at += cut
+            if eof and not keep:
+                return
+
+
+def _parse_line_number(path, offset):
+    """the 1-based number of the line that holds byte ``offset`` of the file: the error path counts newlines on the host"""
+    n, left = 1, offset
+    with open(path, "rb") as f:
+        while left > 0:
+            b = f.read(min(left, 1 << 24))
+            if not b:
+                break
+            n += b.count(b"\n"); left -= len(b)
+    return n
+
+
+def _parse_file(L, text, path, fmt, columns, dev, block_bytes):
+    """the columns of one file, a list of dicts (one per piece), parsed on ``dev`` by k_parse_len / k_parse_fill"""
+    import torch
+    fill = L.md_text_parse_fill_cytosines if fmt == PARSE_CYTOSINE_REPORT else L.md_text_parse_fill_calls
+    out = []
+    for pin, n, at in _parse_pieces(path, block_bytes):
+        d = torch.empty(n, dtype=torch.uint8, device=dev)
+        d.copy_(pin[:n], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()             # the text is complete, and the pinned buffer may take the next piece
+        rows = C.c_int64()
+        rc = L.md_text_parse_measure(text.h, C.c_void_p(d.data_ptr()), n, fmt, C.byref(rows))
+        if rc:
+            raise _rc_error("md_text_parse_measure", rc, L.md_dev_last_error().decode())
+        cols = {name: torch.empty(rows.value * (3 if name == "trinucleotide" else 1), dtype=getattr(torch, dt), device=dev) for name, dt in columns}
+        rc = fill(text.h, C.byref(md_text_cols(*[C.c_void_p(cols[name].data_ptr()) for name, _ in columns])), rows.value)
+        if rc:
+            detail, off = L.md_dev_last_error().decode(), int(L.md_text_parse_error_offset(text.h))
+            if off >= 0:
+                detail = f"{path}, line {_parse_line_number(path, at + off)}: {detail}"
+            else:
+                detail = f"{path}: {detail}"
+            raise _rc_error("reading", rc, detail)
+        out.append(cols)
+    return out
+
+
+def _parse_cat(pieces, columns, dev):
+    import torch
+    cols = {}
+    for name, dt in columns:
+        parts = [p[name] for p in pieces]
+        cols[name] = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.empty(0, dtype=getattr(torch, dt), device=dev)
+    return cols
+
+
+def _contexts_present(context):
+    import torch
+    return tuple(int(k) for k in torch.unique(context).cpu().tolist())
+
+
 class Calls(_Columns):
     """The rows `extract` would print, as columns (one entry per call, in the order of the chunks of the schedule; within a context,
     ascending `start`): ``contig`` (int32, index into ``contigs``, BAM header order), ``start``/``end`` (int32, bedGraph columns 2-3),
@@ -960,6 +1150,42 @@ class Calls(_Columns):
         if self.merged:
             raise MdkError("merge_context: these rows are merged already (merged is true)")
         return self._merged([getattr(self, name) for name, _ in CALL_COLUMNS], min_depth)
+
+    @classmethod
+    def read(cls, paths, reference, device=0, contexts_on=None, block_bytes=None):
+        """The rows of per-cytosine bedGraph files -- what ``write`` made, last week's run, the command-line tool's output -- as a Calls on
+        ``device``, parsed there (csrc/mdk_parse.hip): no line passes through Python.  ``paths`` is one path or a list; the rows come in the
+        order of the paths, then of the lines (``sorted()`` makes the three per-context files of one run the ascending table
+        ``merge_context`` wants).  ``reference`` is a ``Reference``: ``contigs`` is its names, and every row's ``strand`` and ``context``
+        come from its bases at the line's start by the rule of the `mergeContext` command, which is a session's own.  ``merged`` is False;
+        ``contexts_on`` defaults to the contexts that have rows.  The result shares the reference's renderer, so ``write`` and
+        ``merge_context`` need no second one: ``Calls.read(f, ref).merge_context().write(p)`` is the `mergeContext` command.
+        A file is read in pieces of ``block_bytes`` (default 256 MiB), each cut after its last newline, put into a pinned buffer and copied
+        to the device once; a line longer than a piece raises MdkError.  `track` lines are skipped wherever they stand.  The parser is
+        stricter than the command (signs, blanks, doubled tabs, extra columns, numbers past INT32_MAX, merged files and lines longer than
+        512 bytes are refused): MdkError with ``rc == -3`` names the refusal, the path and the line.  Only bedGraph files hold both counts:
+        --fraction, --counts and --methylKit files cannot be read, and neither can .gz files.  There is no CPU path."""
+        dev = _parse_device(device)
+        if not isinstance(reference, Reference):
+            raise MdkError("Calls.read needs a Reference: a bedGraph line's strand and context come from its bases")
+        paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+        block_bytes = _parse_block_bytes(block_bytes)
+        text = reference._renderer(device)
+        pieces = []
+        for p in paths:
+            pieces += _parse_file(text.L, text, os.fspath(p), PARSE_BEDGRAPH, CALL_COLUMNS, dev, block_bytes)
+        cols = _parse_cat(pieces, CALL_COLUMNS, dev)
+        c = cls(list(reference.contigs), cols, merged=False, contexts_on=_contexts_present(cols["context"]) if contexts_on is None else contexts_on)
+        c._text = text
+        return c
+
+    def sorted(self):
+        """the rows in ascending (contig, start): a ``select`` by the stable argsort of contig << 32 | start, in torch"""
+        import torch
+        key = (self.contig.to(torch.int64) << 32) | self.start.to(torch.int64)
+        c = self.select(torch.argsort(key, stable=True))
+        c._text = getattr(self, "_text", None)
+        return c
 
     def rows(self, context=None):
         """(chrom, start, end, nmeth, nunmeth) tuples on the host, optionally of one context -- the bedGraph lines' columns 1, 2, 3, 5, 6"""
@@ -1154,6 +1380,25 @@ class Cytosines(_Columns):
         """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  Returns the path."""
         name = f"{prefix}.cytosine_report.txt"
         return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows)
+
+    @classmethod
+    def read(cls, path, contigs, device=0, contexts_on=None, block_bytes=None):
+        """The rows of a <prefix>.cytosine_report.txt as a Cytosines on ``device``, parsed there (csrc/mdk_parse.hip), in the file's order.
+        ``contigs`` is the list of names the lines' first column is looked up in (a session result's ``contigs``, a ``Reference``'s); no
+        reference is needed: strand, context and trinucleotide are in the file.  ``contexts_on`` defaults to the contexts that have rows.
+        Pieces, refusals and errors as ``Calls.read``; .gz files cannot be read, and there is no CPU path.  Reports of several samples
+        read this way stack as a session's do: ``torch.stack([a.nmeth, b.nmeth])``."""
+        dev = _parse_device(device)
+        block_bytes = _parse_block_bytes(block_bytes)
+        contigs = list(contigs)
+        L = _text_lib()
+        text = _TextRenderer(L, int(device), contigs)
+        cols = _parse_cat(_parse_file(L, text, os.fspath(path), PARSE_CYTOSINE_REPORT, CYTOSINE_COLUMNS, dev, block_bytes), CYTOSINE_COLUMNS, dev)
+        cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
+        c = cls(contigs, cols)
+        c.contexts_on = _contexts_present(cols["context"]) if contexts_on is None else tuple(contexts_on)
+        c._text = text
+        return c
 
     def merge_context(self):
         """The report per CpG / CHG site: a Calls (``merged`` true) with a row for every CpG and CHG site and every CHH cytosine of the

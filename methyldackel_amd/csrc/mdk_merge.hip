@@ -95,7 +95,7 @@ static int merge_status(md_text *t, const char *what) {
 extern "C" int md_text_merge_measure(md_text *t, const md_calls_cols *c, int64_t n, int32_t min_depth, int64_t *rows) {
     const char *const what = "md_text_merge_measure";
     if(!t || !c || !rows || n < 0 || n > TEXT_MAX_ROWS || min_depth < 0) return fail(MDK_ERR_ARG, what, hipSuccess);
-    *rows = 0; t->measured = false; t->merge_measured = false;
+    *rows = 0; t->measured = false; t->merge_measured = false; t->parse_measured = false;
     if(n && (!c->contig || !c->start || !c->end || !c->nmeth || !c->nunmeth || !c->context || !c->strand)) return fail(MDK_ERR_ARG, what, hipSuccess);
     const uint32_t nb = (uint32_t)((n + TEXT_WG - 1) / TEXT_WG);
     HIPCHK(hipSetDevice(t->device));

@@ -28,8 +28,8 @@
 //                  image and streamed out in the same way
 // k_text_fill re-checks every workgroup's total against what k_text_len recorded: columns that changed between the two calls end the fill
 // with an error instead of a write past the buffer.
-// The handle, the argument blocks and the scan of the block table are in mdk_text_internal.hpp: mdk_merge.hip (mergeContext over rows) works
-// on the same handle.
+// The handle, the argument blocks and the scan of the block table are in mdk_text_internal.hpp: mdk_merge.hip (mergeContext over rows) and
+// mdk_parse.hip (text read back into columns) work on the same handle.
 #include "mdk_text_internal.hpp"
 #include "mdk_text_core.h"
 #include <string>
@@ -240,6 +240,7 @@ extern "C" void md_text_close(md_text *t) {
     if(!t) return;
     (void)hipSetDevice(t->device);
     if(t->st) { (void)hipStreamSynchronize(t->st); (void)hipStreamDestroy(t->st); }
+    text_parse_free(t);
     (void)hipFree(t->d_name_off); (void)hipFree(t->d_names); (void)hipFree(t->d_btot); (void)hipFree(t->d_boff); (void)hipFree(t->d_st);
     if(t->h_st) (void)hipHostFree(t->h_st);
     delete t;
@@ -277,7 +278,7 @@ int text_blocks_reserve(md_text *t, uint32_t nb) {
 
 static int text_measure(md_text *t, const TextView &v, int64_t r0, int64_t r1, int fmt, int context, int64_t *bytes, const char *what) {
     if(!t || !bytes || r0 < 0 || r1 < r0 || r1 - r0 > TEXT_MAX_ROWS || context < -1 || context > 2) return fail(MDK_ERR_ARG, what, hipSuccess);
-    *bytes = 0; t->measured = false; t->merge_measured = false;
+    *bytes = 0; t->measured = false; t->merge_measured = false; t->parse_measured = false;
     const uint32_t n = (uint32_t)(r1 - r0), nb = (n + TEXT_WG - 1) / TEXT_WG;
     if(n && (!v.contig || !v.a || !v.m || !v.u || !v.ctx || !v.strand || (fmt == MD_TEXT_CYTOSINE_REPORT ? !v.tri : !v.b))) return fail(MDK_ERR_ARG, what, hipSuccess);
     HIPCHK(hipSetDevice(t->device));
@@ -300,7 +301,7 @@ static int text_measure(md_text *t, const TextView &v, int64_t r0, int64_t r1, i
 extern "C" int md_text_measure_reads(md_text *t, const md_reads_cols *c, int64_t n_name_bytes, int64_t r0, int64_t r1, int64_t *bytes) {
     const char *const what = "md_text_measure_reads";
     if(!t || !c || !bytes || n_name_bytes < 0 || r0 < 0 || r1 < r0 || r1 - r0 > TEXT_MAX_ROWS) return fail(MDK_ERR_ARG, what, hipSuccess);
-    *bytes = 0; t->measured = false; t->merge_measured = false;
+    *bytes = 0; t->measured = false; t->merge_measured = false; t->parse_measured = false;
     const uint32_t n = (uint32_t)(r1 - r0), nb = (n + TEXT_WG - 1) / TEXT_WG;
     if(n && (!c->contig || !c->pos || !c->nmeth || !c->nunmeth || !c->name_off || (n_name_bytes && !c->name_bytes))) return fail(MDK_ERR_ARG, what, hipSuccess);
     HIPCHK(hipSetDevice(t->device));

@@ -1,4 +1,5 @@
-// mdk_text_internal.hpp -- what the two sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows): the
+// mdk_text_internal.hpp -- what the sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows;
+// mdk_parse.hip: text read back into columns): the
 // handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
 // scan of the block table.
 #ifndef MDK_TEXT_INTERNAL_HPP
@@ -9,7 +10,7 @@
 #define TEXT_SCAN_WG 1024
 #define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
 
-struct TextStatus { int64_t total; uint32_t err, pad; };
+struct TextStatus { int64_t total; uint32_t err, pad; unsigned long long first; };      // first: mdk_parse.hip, the refused line that starts earliest (offset << 8 | refusal)
 // the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
 struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
 struct KText {
@@ -36,6 +37,15 @@ struct KMerge {
     md_calls_cols dst; int64_t rows;
 };
 
+// text read back into columns (mdk_parse.hip): the measured text, what its lines are looked up in, and where the fill writes
+struct KParse {
+    const uint8_t *text; int64_t bytes; int32_t fmt, n_contigs;
+    const uint32_t *name_off; const uint8_t *names; const uint32_t *sorted;      // sorted: the contig indices in ascending order of their names
+    const uint8_t *const *ref; const int64_t *ref_len;                            // the resident bases per contig (ref_len < 0: none)
+    uint32_t *btot; int64_t *boff; TextStatus *st;
+    md_calls_cols calls; md_cytosines_cols cyto; int64_t rows;
+};
+
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
     uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
@@ -43,10 +53,17 @@ struct md_text {
     TextStatus *d_st = nullptr, *h_st = nullptr;
     KText K; KReads R; bool measured = false, reads = false;          // reads: the range measured last is one of md_text_measure_reads
     KMerge M; bool merge_measured = false;                            // the block table holds md_text_merge_measure's totals (one table: a measure of either kind voids the other's)
+    KParse P; bool parse_measured = false;                            // ... or md_text_parse_measure's
+    uint32_t *d_sorted = nullptr;                                     // mdk_parse.hip, made by the first parse: the name index
+    std::vector<uint8_t *> ref; std::vector<int64_t> ref_len;         // md_text_reference: the contigs' bases on the device (host copies of the two tables below)
+    uint8_t **d_ref = nullptr; int64_t *d_ref_len = nullptr;
+    long long parse_error_offset = -1;
 };
 
 // the block table for nb workgroups
 MDK_HIDDEN int text_blocks_reserve(md_text *t, uint32_t nb);
+// md_text_close: what mdk_parse.hip hung on the handle
+MDK_HIDDEN void text_parse_free(md_text *t);
 
 // one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
 __device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
