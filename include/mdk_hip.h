@@ -61,7 +61,20 @@ typedef struct {
  * The payload of a read lives at blob + 4*off4:
  *   uint8 seq[(l_qseq+1)/2]   BAM 4-bit codes, high nibble = even query index; padded to a multiple of 4 bytes
  *   uint8 qual[l_qseq]        raw phred bytes; padded to a multiple of 4 bytes
- * Segments are emitted in file (coordinate) order of their reads, ascending within a read. */
+ * The host preparation emits segments in file (coordinate) order of their reads, ascending within a read; the device does not rely
+ * on it.  What a caller-built batch may hold (tests/test_gpu_pileup_kernel.py pins it):
+ *   - segments in any order, any number of them on one position; a tile works through the run of the array between the first and the
+ *     last segment that touches it and passes over what lies between them without touching it;
+ *   - rpos >= 0, len >= 1, q0 + len <= l_qseq and, with MDK_SF_PARTNER, m_q0 + len <= m_l_qseq: every payload index a segment can name
+ *     lies inside the payload, which lies inside the blob.  Nothing else is required of q0, m_q0 or the two reads' lengths;
+ *   - a segment may start before beg, end after end or run past the contig's end: only its positions p with beg <= p < end and
+ *     p < contig length are counted.  A segment with none, n_segs == 0 and beg == end are all fine and give no sites;
+ *   - trimming windows (md_dev_cfg bounds / absoluteBounds) may be empty or wider than the read; a base outside its read's window, own
+ *     or partner's, reads as N with quality 0 -- the partner's window is that of the partner's strand and read number (msf);
+ *   - a segment of strand 0 (undeterminable) has no trimming window and matches no '+' or '-' run of md_dev_set_regions.  Where it
+ *     covers a position at which its own strand would be called -- a G site, as for OB/CTOB -- the launch fails with MDK_ERR_STRAND0,
+ *     whatever the base and its quality; over C sites it is opposite-strand evidence when minOppositeDepth > 0, and nothing otherwise.
+ *     The error belongs to that launch: md_dev_download returns it once and the slot takes the next batch as any other. */
 typedef struct {
     int32_t  rpos;       /* reference position of the segment's first base */
     uint32_t off4;       /* payload of the read the segment belongs to */
