@@ -548,6 +548,25 @@ void md_text_close(md_text *t);
 int  md_text_merge_measure(md_text *t, const md_calls_cols *cols, int64_t n, int32_t min_depth, int64_t *rows);
 int  md_text_merge_fill(md_text *t, const md_calls_cols *dst, int64_t rows);
 
+/* ---- sums over intervals: rows added up per island, promoter, candidate DMR or tile (csrc/mdk_regions.hip, csrc/mdk_region_core.h) ----
+ * The n rows of DEVICE-resident md_calls_cols (n at most 2^30; `end` is not read and may be NULL) must be strictly ascending in (contig,
+ * start).  The k intervals (k at most 2^30) are three int32 DEVICE columns, half-open and 0-based as BED lines, in any order; they may
+ * overlap, nest or repeat.  With lo_j the number of rows whose (contig, start) < (iv_contig[j], iv_start[j]) and hi_j the number whose
+ * (contig, start) < (iv_contig[j], iv_end[j]), the rows of interval j are [lo_j, hi_j): a row belongs to the interval that holds its
+ * start, a merged row wider than one base included, so the windows of a tiling count every row exactly once.  A row counts if bit `context`
+ * of context_mask (3 bits) is set, its strand is allowed by strand_mask (bit 0: +1, bit 1: -1, bit 2: 0, a merged row) and nmeth + nunmeth,
+ * formed in 64 bits, is at least min_depth (not negative).  Per interval, in the intervals' own order, into DEVICE memory of k entries each:
+ * nsites (the rows counted), nmeth and nunmeth (their counts added, int64).  An empty interval and one without rows give zeros.
+ * MDK_ERR_ARG, with md_dev_last_error naming it, for rows not strictly ascending, a row's contig outside the name table, a context above 2,
+ * an interval's contig outside the name table, an interval with start < 0 or end < start; the contents of the outputs are unspecified
+ * then, and nothing is written past them.  One call, synchronous on the renderer's stream, with the rules of the sections above (one thread
+ * at a time, the columns complete when the call is made).  It keeps a table of its own on the renderer (20 bytes per 256 rows, until
+ * md_text_close) and voids nothing: a text, merge or parse measure that waits for its fill on the same renderer stays valid. */
+int  md_text_regions(md_text *t, const md_calls_cols *cols, int64_t n,
+                     const int32_t *iv_contig, const int32_t *iv_start, const int32_t *iv_end, int64_t k,
+                     uint32_t context_mask, uint32_t strand_mask, int32_t min_depth,
+                     int32_t *nsites, int64_t *nmeth, int64_t *nunmeth);
+
 /* ---- text read back into columns: a bedGraph or a cytosine report parsed on the device (csrc/mdk_parse.hip, csrc/mdk_parse_core.h) ----
  * The way back from md_text_fill: `bytes` bytes of text in DEVICE memory become rows in the layouts above, without the host looking at a line.
  * A line starts at byte 0 and after every '\n' and ends before the next '\n' or at the end of the text; one '\r' before the '\n' is dropped; a

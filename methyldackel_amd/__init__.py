@@ -179,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill",
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions",
                "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
@@ -702,6 +702,8 @@ def _text_lib():
         L.md_text_close.argtypes = [C.c_void_p]; L.md_text_close.restype = None
         L.md_text_merge_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.md_text_merge_fill.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
+        L.md_text_regions.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.md_text_reference.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.md_text_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
         L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
@@ -848,6 +850,52 @@ class _Columns:
         if rc:
             raise _rc_error("md_text_merge_fill", rc, L.md_dev_last_error().decode())
         return Calls(self.contigs, out, merged=True, contexts_on=self.contexts_on)
+
+    def _regions(self, cols, intervals, contexts, strand, min_depth):
+        """the sums of ``cols`` -- this object's rows as the seven tensors of CALL_COLUMNS -- over ``intervals`` on the rows' device
+        (k_region_rows / k_region_blocks / k_region_sum, csrc/mdk_regions.hip): a Regions of the intervals' tensors and three new ones"""
+        import torch
+        if not isinstance(intervals, Intervals):
+            raise MdkError("regions needs an Intervals (Intervals.read, Intervals.windows)")
+        if list(intervals.contigs) != list(self.contigs):
+            raise MdkError("the intervals' contigs are not the rows' contigs: their indices would name other sequences")
+        if contexts is None:
+            contexts = (0, 1, 2)
+        context_mask = 0
+        for x in ([contexts] if isinstance(contexts, (str, int)) else contexts):
+            if x in CONTEXT_FILES:
+                x = CONTEXT_FILES.index(x)
+            if isinstance(x, bool) or x not in (0, 1, 2):
+                raise MdkError(f"unknown context {x!r}: a subset of {CONTEXT_FILES}, or of the indices 0 to 2")
+            context_mask |= 1 << x
+        if strand not in (None, "+", "-"):
+            raise MdkError(f"unknown strand {strand!r}: None (any), '+' or '-'")
+        strand_mask = {None: 7, "+": 1, "-": 2}[strand]
+        min_depth = int(min_depth)
+        if not 0 <= min_depth <= 2 ** 31 - 1:
+            raise MdkError("min_depth must be between 0 and 2^31 - 1")
+        dev, n = cols[0].device, int(cols[0].shape[0])
+        for t, (name, dt) in zip(cols, CALL_COLUMNS):
+            if t.device.type != "cuda":
+                raise MdkError(f"regions are summed on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+            if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        iv = intervals.to(dev)
+        k = len(iv)
+        for name in ("contig", "start", "end"):
+            t = getattr(iv, name)
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != k:
+                raise MdkError(f"the intervals' {name} column must be a contiguous int32 tensor with one entry per interval")
+        L = self._renderer(dev)
+        out = {"contig": iv.contig, "start": iv.start, "end": iv.end, "nsites": torch.empty(k, dtype=torch.int32, device=dev),
+               "nmeth": torch.empty(k, dtype=torch.int64, device=dev), "nunmeth": torch.empty(k, dtype=torch.int64, device=dev)}
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        view = md_text_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
+        rc = L.md_text_regions(self._text.h, C.byref(view), n, C.c_void_p(iv.contig.data_ptr()), C.c_void_p(iv.start.data_ptr()), C.c_void_p(iv.end.data_ptr()), k,
+                               context_mask, strand_mask, min_depth, C.c_void_p(out["nsites"].data_ptr()), C.c_void_p(out["nmeth"].data_ptr()), C.c_void_p(out["nunmeth"].data_ptr()))
+        if rc:
+            raise _rc_error("md_text_regions", rc, L.md_dev_last_error().decode())
+        return Regions(list(self.contigs), out)
 
     def _text_iter(self, L, view, dev, fmt, context, block_rows):
         import torch
@@ -1151,6 +1199,20 @@ class Calls(_Columns):
             raise MdkError("merge_context: these rows are merged already (merged is true)")
         return self._merged([getattr(self, name) for name, _ in CALL_COLUMNS], min_depth)
 
+    def regions(self, intervals, contexts=None, strand=None, min_depth=1):
+        """These rows added up per interval -- CpG islands, promoters, a BED of candidate DMRs, the tiles every DMR tool starts from --: a
+        ``Regions`` with, per interval and in the intervals' own order, ``nsites`` (the rows counted), ``nmeth`` and ``nunmeth`` (int64),
+        made on the rows' device (csrc/mdk_regions.hip) from the columns as they are: no file, no key per row, no prefix sum per row.
+        ``intervals`` is an ``Intervals`` over the same ``contigs`` (on the CPU it is moved to the rows' device); its intervals may come
+        in any order and overlap, nest or repeat.  A row belongs to the interval that holds its ``start`` -- a ``merge_context`` row,
+        wider than one base, too --, so the windows of a tiling count every row exactly once.  A row counts if its context is in
+        ``contexts`` (any subset of ("CpG", "CHG", "CHH") or of the indices 0 to 2; default: all), its strand is ``strand`` (``None``:
+        any, merged rows included; "+" or "-") and nmeth + nunmeth >= ``min_depth``.  The rows must be strictly ascending in (contig,
+        start), as a session returns them: rows in another order, a context above 2, a contig index outside ``contigs`` and an
+        interval with a contig outside them, ``start < 0`` or ``end < start`` raise MdkError (rc -3); so do CPU tensors: there is no CPU
+        path."""
+        return self._regions([getattr(self, name) for name, _ in CALL_COLUMNS], intervals, contexts, strand, min_depth)
+
     @classmethod
     def read(cls, paths, reference, device=0, contexts_on=None, block_bytes=None):
         """The rows of per-cytosine bedGraph files -- what ``write`` made, last week's run, the command-line tool's output -- as a Calls on
@@ -1408,11 +1470,120 @@ class Cytosines(_Columns):
         CpGs matrix.  ``Calls.render`` prints no line for an uncovered row."""
         return self._merged([self.contig, self.pos - 1, self.pos, self.nmeth, self.nunmeth, self.context, self.strand], 0)
 
+    def regions(self, intervals, contexts=None, strand=None, min_depth=0):
+        """The report added up per interval: ``Calls.regions`` over a view of these columns (``start`` = pos - 1, ``end`` = pos; counts,
+        contig, context and strand are not copied).  At the default ``min_depth=0`` ``nsites`` is the number of cytosines of the
+        interval, at ``min_depth=1`` the number covered; with ``Intervals.windows`` two samples' results line up window for window."""
+        return self._regions([self.contig, self.pos - 1, self.pos, self.nmeth, self.nunmeth, self.context, self.strand], intervals, contexts, strand, min_depth)
+
     def rows(self):
         """(chrom, pos, "+"/"-", nmeth, nunmeth, "CG"/"CHG"/"CHH", trinucleotide) tuples on the host: the seven fields of a line"""
         cols = [getattr(self, n).cpu().tolist() for n in ("contig", "pos", "strand", "nmeth", "nunmeth", "context")]
         tri = self.trinucleotide.cpu().numpy().tobytes().decode("latin-1")
         return [(self.contigs[c], p, "+" if s > 0 else "-", m, u, CONTEXTS[x], tri[3 * i:3 * i + 3]) for i, (c, p, s, m, u, x) in enumerate(zip(*cols))]
+
+
+REGION_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nsites", "int32"), ("nmeth", "int64"), ("nunmeth", "int64"))
+MAX_INTERVALS = 1 << 30
+
+
+class Intervals:
+    """Half-open, 0-based intervals as a BED file has them, for ``Calls.regions`` / ``Cytosines.regions``: ``contigs`` (the names the
+    indices mean) and three int32 tensors of one entry per interval, ``contig`` (index into ``contigs``), ``start`` and ``end``, in any
+    order; intervals may overlap, nest or repeat."""
+
+    def __init__(self, contigs, contig, start, end):
+        self.contigs = list(contigs)
+        self.contig, self.start, self.end = contig, start, end
+
+    def __len__(self):
+        return int(self.contig.shape[0])
+
+    def to(self, device):
+        """the same intervals with their three tensors on ``device`` (this object if they are there already)"""
+        cols = [t.to(device) for t in (self.contig, self.start, self.end)]
+        if all(a is b for a, b in zip(cols, (self.contig, self.start, self.end))):
+            return self
+        return Intervals(self.contigs, *cols)
+
+    @classmethod
+    def read(cls, bed_path, contigs):
+        """The intervals of a BED file, on the CPU, in the file's order.  ``contigs`` is the list of names column 1 is looked up in (a
+        session result's ``contigs``, a ``Reference``'s).  Fields are separated by tabs or blanks and only the first three are used;
+        empty lines and lines that begin with ``#``, ``track`` or ``browser`` are skipped.  A contig that is not in ``contigs``, a
+        field that is not a decimal number, ``end < start`` and a value above 2^31 - 1 raise MdkError with the path and the line
+        number.  Parsed on the host, line by line: a BED of islands or promoters has a few 10^5 lines.  .gz files cannot be read."""
+        import torch
+        path, contigs = os.fspath(bed_path), list(contigs)
+        index = {}
+        for i, name in enumerate(contigs):
+            index.setdefault(name, i)
+        cols = ([], [], [])
+        with open(path, "rb") as f:
+            for ln, raw in enumerate(f, 1):
+                fields = raw.decode("latin-1").split()
+                if not fields or fields[0].startswith("#") or fields[0] in ("track", "browser"):
+                    continue
+                if len(fields) < 3:
+                    raise MdkError(f"{path}:{ln}: a BED line has at least three fields")
+                if fields[0] not in index:
+                    raise MdkError(f"{path}:{ln}: the contig {fields[0]!r} is not among the contig names")
+                for v in fields[1:3]:
+                    if not (v.isascii() and v.isdigit()):
+                        raise MdkError(f"{path}:{ln}: {v!r} is not a decimal number")
+                s, e = int(fields[1]), int(fields[2])
+                if s > 2 ** 31 - 1 or e > 2 ** 31 - 1:
+                    raise MdkError(f"{path}:{ln}: a position above 2^31 - 1")
+                if e < s:
+                    raise MdkError(f"{path}:{ln}: end {e} < start {s}")
+                cols[0].append(index[fields[0]]); cols[1].append(s); cols[2].append(e)
+        return cls(contigs, *[torch.tensor(c, dtype=torch.int32) for c in cols])
+
+    @classmethod
+    def windows(cls, lengths, width, step=None, contigs=None):
+        """Every window ``[i * step, min(i * step + width, length))`` of every contig, in contig order, on the CPU -- the tiles of
+        methylKit's ``tileMethylCounts`` (``step == width``, the default) or sliding windows (``step < width``).  ``lengths`` is a
+        ``Reference``, or a list of contig lengths with their names as ``contigs``.  The windows depend on the lengths alone, covered or
+        not, so two samples' ``regions`` line up window for window, as ``cytosine_report`` rows do.  ``width < 1``, ``step < 1`` and
+        more than 2^30 windows raise MdkError."""
+        import torch
+        if isinstance(lengths, Reference):
+            lengths, contigs = lengths.lengths, lengths.contigs if contigs is None else contigs
+        lengths = [int(x) for x in lengths]
+        if contigs is None or len(list(contigs)) != len(lengths):
+            raise MdkError("windows needs a Reference, or a list of lengths and contigs= with a name for each")
+        width, step = int(width), int(width if step is None else step)
+        if width < 1 or step < 1:
+            raise MdkError("width and step must be at least 1")
+        if any(x < 0 or x > 2 ** 31 - 1 for x in lengths):
+            raise MdkError("a contig length must be between 0 and 2^31 - 1")
+        counts = [(x + step - 1) // step for x in lengths]
+        if sum(counts) > MAX_INTERVALS:
+            raise MdkError(f"{sum(counts)} windows: more than 2^30")
+        counts = torch.tensor(counts, dtype=torch.int64)
+        contig = torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int64), counts)
+        first = torch.cumsum(counts, 0) - counts
+        start = (torch.arange(int(counts.sum()), dtype=torch.int64) - first[contig]) * step
+        end = torch.minimum(start + width, torch.tensor(lengths, dtype=torch.int64)[contig])
+        return cls(contigs, contig.to(torch.int32), start.to(torch.int32), end.to(torch.int32))
+
+
+class Regions(_Columns):
+    """What ``Calls.regions`` / ``Cytosines.regions`` return, one entry per interval in the intervals' own order, on the rows' device:
+    ``contig``, ``start``, ``end`` (int32: the intervals' own tensors), ``nsites`` (int32: the rows counted), ``nmeth`` and ``nunmeth``
+    (int64: their counts added).  ``select`` takes a mask, an index or a slice, as for the other results."""
+    COLUMNS = REGION_COLUMNS
+
+    def rows(self):
+        """(chrom, start, end, nsites, nmeth, nunmeth) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n, _ in REGION_COLUMNS]
+        return [(self.contigs[c], a, b, k, m, u) for c, a, b, k, m, u in zip(*cols)]
+
+    def write(self, path):
+        """the six columns, tab-separated, the contig by its name, without a header; formatted on the host.  Returns the path."""
+        with open(path, "w") as f:
+            f.writelines("%s\t%d\t%d\t%d\t%d\t%d\n" % r for r in self.rows())
+        return path
 
 
 class Session:

@@ -1,5 +1,5 @@
 // mdk_text_internal.hpp -- what the sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows;
-// mdk_parse.hip: text read back into columns): the
+// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals): the
 // handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
 // scan of the block table.
 #ifndef MDK_TEXT_INTERNAL_HPP
@@ -46,6 +46,16 @@ struct KParse {
     md_calls_cols calls; md_cytosines_cols cyto; int64_t rows;
 };
 
+// sums of rows over intervals (mdk_regions.hip): the rows, the intervals, the filter, the prefix table of one entry per 256 rows, the result
+struct KRegion {
+    const int32_t *contig, *start, *m, *u; const uint8_t *ctx; const int8_t *strand;
+    uint32_t n; int32_t n_contigs;
+    const int32_t *iv_contig, *iv_start, *iv_end; uint32_t k;
+    uint32_t context_mask, strand_mask; int32_t min_depth;
+    uint32_t *pre_sites; int64_t *pre_m, *pre_u; TextStatus *st;          // nb + 1 entries each: block totals, scanned in place
+    int32_t *nsites; int64_t *nmeth, *nunmeth;
+};
+
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
     uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
@@ -58,12 +68,15 @@ struct md_text {
     std::vector<uint8_t *> ref; std::vector<int64_t> ref_len;         // md_text_reference: the contigs' bases on the device (host copies of the two tables below)
     uint8_t **d_ref = nullptr; int64_t *d_ref_len = nullptr;
     long long parse_error_offset = -1;
+    uint32_t *d_rsites = nullptr; int64_t *d_rm = nullptr, *d_ru = nullptr; size_t cap_rblocks = 0;      // mdk_regions.hip: its prefix table, apart from d_btot / d_boff
 };
 
 // the block table for nb workgroups
 MDK_HIDDEN int text_blocks_reserve(md_text *t, uint32_t nb);
 // md_text_close: what mdk_parse.hip hung on the handle
 MDK_HIDDEN void text_parse_free(md_text *t);
+// ... and mdk_regions.hip
+MDK_HIDDEN void text_regions_free(md_text *t);
 
 // one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
 __device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
