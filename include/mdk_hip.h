@@ -567,6 +567,33 @@ int  md_text_regions(md_text *t, const md_calls_cols *cols, int64_t n,
                      uint32_t context_mask, uint32_t strand_mask, int32_t min_depth,
                      int32_t *nsites, int64_t *nmeth, int64_t *nunmeth);
 
+/* ---- samples joined into one site table: methylKit's `unite` (csrc/mdk_unite.hip, csrc/mdk_unite_core.h) ----
+ * n_samples (1 to 1024) tables of DEVICE-resident md_calls_cols, sample s of n_rows[s] rows (at most 2^30), each strictly ascending in
+ * (contig, start), with starts that are not negative.  A row is present in its sample if nmeth + nunmeth, formed in 64 bits, is at least
+ * min_depth (not negative; 0: every row is).  A site is a (contig, start) of which some sample holds a present row; the result is the
+ * sites at least min_samples (1 to n_samples) samples hold, ascending in (contig, start), with every sample's counts.  No key per row
+ * and no sort: the sites are the bits of a bitmap over the contigs' covered extents -- per contig the largest start + 1 of any sample,
+ * rounded up to 32 --, a site's number is the rank of its bit.  Two steps on a renderer (its stream, its status block, its contig count;
+ * the same rules: synchronous, one thread at a time, the columns complete when the call is made):
+ *   md_text_unite_measure  *n_union = the sites of the union (what min_samples 1 would give), *n_out = the sites of the result.
+ *                          MDK_ERR_ARG, with md_dev_last_error naming it, for rows of a sample not strictly ascending, a contig index
+ *                          outside the name table, a context above 2, a negative start, covered extents that add up to more than 2^35
+ *                          bits (refused before the bitmap is allocated), more than 2^30 sites in the union.  The samples' columns must
+ *                          stay alive and unchanged until the fill.  Temporaries, kept on the renderer until md_text_close: the extents
+ *                          / 4 bytes (bitmap and ranks) and 12 bytes per site of the union;
+ *   md_text_unite_fill     into DEVICE memory of the caller: contig, start, end, context, strand and nsamples (the samples that hold the
+ *                          site) of n_out entries, nmeth and nunmeth of n_samples x n_out entries, sample-major -- row s is sample s --,
+ *                          which the call sets to zero first: a sample that does not hold a site has 0 0 there.  n_out must be the
+ *                          measured number.  The site's end, context and strand are those of one of the samples' rows, and every other
+ *                          present row of the site is compared with them: MDK_ERR_ARG "samples disagree about a site" for a difference
+ *                          (tables made against one reference never differ).  Columns that changed since the measure end the call with
+ *                          MDK_ERR_ARG or give other numbers; nothing is written outside the outputs.
+ * The tables are this section's own: a text, merge or parse measure that waits for its fill on the same renderer stays valid. */
+int  md_text_unite_measure(md_text *t, const md_calls_cols *samples, int32_t n_samples, const int64_t *n_rows, int32_t min_samples, int32_t min_depth,
+                           int64_t *n_union, int64_t *n_out);
+int  md_text_unite_fill(md_text *t, int32_t *contig, int32_t *start, int32_t *end, uint8_t *context, int8_t *strand, int32_t *nsamples,
+                        int32_t *nmeth, int32_t *nunmeth, int64_t n_out);
+
 /* ---- text read back into columns: a bedGraph or a cytosine report parsed on the device (csrc/mdk_parse.hip, csrc/mdk_parse_core.h) ----
  * The way back from md_text_fill: `bytes` bytes of text in DEVICE memory become rows in the layouts above, without the host looking at a line.
  * A line starts at byte 0 and after every '\n' and ends before the next '\n' or at the end of the text; one '\r' before the '\n' is dropped; a

@@ -179,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions",
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill",
                "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
@@ -704,6 +704,8 @@ def _text_lib():
         L.md_text_merge_fill.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
         L.md_text_regions.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.md_text_unite_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.md_text_unite_fill.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int64]
         L.md_text_reference.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.md_text_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
         L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
@@ -1584,6 +1586,125 @@ class Regions(_Columns):
         with open(path, "w") as f:
             f.writelines("%s\t%d\t%d\t%d\t%d\t%d\n" % r for r in self.rows())
         return path
+
+
+SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"), ("nsamples", "int32"))
+MAX_SAMPLES = 1024
+
+
+class Cohort:
+    """What ``unite`` returns: the sites several samples hold, one entry per site, ascending in (contig, start), on the samples' device.
+    ``contig``, ``start``, ``end`` (int32), ``context`` (uint8) and ``strand`` (int8) describe the site as a Calls row does; ``nsamples``
+    (int32) is the number of samples that hold it after the depth cut; ``nmeth`` and ``nunmeth`` are int32 matrices ``[S, n]``, row s the
+    counts of sample s, zeros where it does not hold the site.  ``contigs`` and ``merged`` are the samples', ``contexts_on`` the union of
+    theirs; ``n_union`` is the number of sites any sample holds, which ``min_samples=1`` would have given."""
+
+    def __init__(self, contigs, columns, nmeth, nunmeth, merged=False, contexts_on=(0, 1, 2), n_union=None):
+        self.contigs = contigs
+        for name, _ in SITE_COLUMNS:
+            setattr(self, name, columns[name])
+        self.nmeth, self.nunmeth = nmeth, nunmeth
+        self.merged, self.contexts_on = bool(merged), tuple(contexts_on)
+        self.n_union = len(self) if n_union is None else int(n_union)
+        self._text = None
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    @property
+    def n_samples(self):
+        return int(self.nmeth.shape[0])
+
+    def select(self, index):
+        """a copy with the sites ``column[index]`` (a boolean mask, an index tensor, a slice): of the site columns, and of the matrices
+        along their site axis"""
+        cols = {name: getattr(self, name)[index].contiguous() for name, _ in SITE_COLUMNS}
+        c = Cohort(self.contigs, cols, self.nmeth[:, index].contiguous(), self.nunmeth[:, index].contiguous(), self.merged, self.contexts_on, self.n_union)
+        c._text = self._text
+        return c
+
+    def sample(self, i):
+        """Sample ``i`` over ALL the sites of the table, as a Calls: the site columns and row ``i`` of the two matrices -- views, not
+        copies.  A site the sample does not hold is a ``0 0`` row, which ``regions`` (at ``min_depth`` >= 1), ``write`` and
+        ``merge_context`` pass over as they pass over any such row; so ``cohort.sample(i).regions(tiles)`` lines up across samples."""
+        i = int(i)
+        if not 0 <= i < self.n_samples:
+            raise MdkError(f"sample {i}: the table holds samples 0 to {self.n_samples - 1}")
+        cols = {name: getattr(self, name) for name, _ in CALL_COLUMNS if name not in ("nmeth", "nunmeth")}
+        cols["nmeth"], cols["nunmeth"] = self.nmeth[i], self.nunmeth[i]
+        c = Calls(self.contigs, cols, merged=self.merged, contexts_on=self.contexts_on)
+        c._text = self._text
+        return c
+
+    def rows(self):
+        """(chrom, start, end, context, strand, nsamples, (nmeth, nunmeth) of sample 0, of sample 1, ...) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n, _ in SITE_COLUMNS]
+        m, u = self.nmeth.t().cpu().tolist(), self.nunmeth.t().cpu().tolist()
+        return [(self.contigs[c], a, b, x, s, k) + tuple(zip(mm, uu)) for (c, a, b, x, s, k), mm, uu in zip(zip(*cols), m, u)]
+
+
+def unite(samples, min_samples=None, min_depth=1):
+    """Several samples' calls joined into one table of sites -- what methylKit calls ``unite`` and every comparison of samples starts
+    from: a ``Cohort`` of the sites at least ``min_samples`` of the samples hold (default: all of them; 1: the union), with every
+    sample's counts per site, made on the samples' device (csrc/mdk_unite.hip) from the columns as they are: no key per row, no sort.
+    ``samples`` is a sequence of 1 to 1024 ``Calls`` on one device with the same ``contigs`` and the same ``merged``; a row whose
+    nmeth + nunmeth is below ``min_depth`` counts as absent from its sample (0 keeps ``0 0`` rows).  Every sample must be strictly
+    ascending in (contig, start), as a session returns it, and the samples must agree about a site: for one (contig, start) the same
+    ``end``, ``context`` and ``strand`` -- runs against one reference do; a merged CpG table and a merged CHG table do not, and cannot
+    be united into one (nor can either be with per-strand rows: ``merged`` must be the same).  Rows in another order, a context above
+    2, a contig index outside ``contigs``, a negative start, samples that disagree about a site of the result, and sites spread over
+    more than 2^35 bases of covered extent raise MdkError (rc -3); so do CPU tensors: there is no CPU path."""
+    import torch
+    samples = list(samples)
+    S = len(samples)
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"unite takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if not all(isinstance(c, Calls) for c in samples):
+        raise MdkError("unite takes Calls (Session.extract, Calls.read, merge_context, select)")
+    first = samples[0]
+    for k, c in enumerate(samples):
+        if list(c.contigs) != list(first.contigs):
+            raise MdkError(f"sample {k}'s contigs are not sample 0's: their indices would name other sequences")
+        if c.merged != first.merged:
+            raise MdkError(f"sample {k} has merged={c.merged}, sample 0 merged={first.merged}: merged and per-strand rows describe different sites")
+    min_samples = S if min_samples is None else int(min_samples)
+    if not 1 <= min_samples <= S:
+        raise MdkError(f"min_samples must be between 1 and the number of samples, {S}")
+    min_depth = int(min_depth)
+    if not 0 <= min_depth <= 2 ** 31 - 1:
+        raise MdkError("min_depth must be between 0 and 2^31 - 1")
+    dev = first.start.device
+    for k, c in enumerate(samples):
+        n = int(c.start.shape[0]) if c.start.dim() else -1
+        for name, dt in CALL_COLUMNS:
+            t = getattr(c, name)
+            if t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+                raise MdkError(f"sample {k}: the {name} column must be a contiguous {dt} tensor with one entry per row")
+    for k, c in enumerate(samples):
+        for name, _ in CALL_COLUMNS:
+            t = getattr(c, name)
+            if t.device.type != "cuda":
+                raise MdkError(f"samples are united on the device: the {name} column of sample {k} is a {t.device.type} tensor, and there is no CPU path")
+            if t.device != dev:
+                raise MdkError(f"sample {k}: the {name} column is on {t.device}, sample 0 on {dev}")
+    L = first._renderer(dev)
+    text = first._text
+    torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+    views = (md_text_cols * S)(*[md_text_cols(*[C.c_void_p(getattr(c, name).data_ptr()) for name, _ in CALL_COLUMNS]) for c in samples])
+    n_rows = (C.c_int64 * S)(*[len(c) for c in samples])
+    n_union, n_out = C.c_int64(), C.c_int64()
+    rc = L.md_text_unite_measure(text.h, views, S, n_rows, min_samples, min_depth, C.byref(n_union), C.byref(n_out))
+    if rc:
+        raise _rc_error("md_text_unite_measure", rc, L.md_dev_last_error().decode())
+    n = n_out.value
+    cols = {name: torch.empty(n, dtype=getattr(torch, dt), device=dev) for name, dt in SITE_COLUMNS}
+    nmeth, nunmeth = (torch.empty((S, n), dtype=torch.int32, device=dev) for _ in range(2))
+    rc = L.md_text_unite_fill(text.h, *[C.c_void_p(cols[name].data_ptr()) for name, _ in SITE_COLUMNS], C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), n)
+    if rc:
+        raise _rc_error("md_text_unite_fill", rc, L.md_dev_last_error().decode())
+    out = Cohort(list(first.contigs), cols, nmeth, nunmeth, first.merged, sorted(set().union(*[c.contexts_on for c in samples])), n_union.value)
+    out._text = text
+    return out
 
 
 class Session:

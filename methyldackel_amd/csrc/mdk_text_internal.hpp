@@ -1,5 +1,5 @@
 // mdk_text_internal.hpp -- what the sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows;
-// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals): the
+// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals; mdk_unite.hip: samples joined into one site table): the
 // handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
 // scan of the block table.
 #ifndef MDK_TEXT_INTERNAL_HPP
@@ -56,6 +56,18 @@ struct KRegion {
     int32_t *nsites; int64_t *nmeth, *nunmeth;
 };
 
+// samples joined into one site table (mdk_unite.hip): a sample's columns and rows; the samples, the tables of mdk_unite_core.h, the result
+struct UniSample { const int32_t *contig, *start, *end, *m, *u; const uint8_t *ctx; const int8_t *strand; uint32_t n, pad; };
+struct KUnite {
+    const UniSample *S; int32_t n_samples, n_contigs, min_samples, min_depth;
+    uint32_t *extent; int64_t *base;                                      // per contig: bits covered, first word
+    uint32_t *bits, *rankw, *btot; int64_t n_words;                       // n_words: a multiple of UNI_BLOCK_WORDS; btot: an entry per UNI_BLOCK_WORDS words, scanned in place
+    uint32_t *count, *owner, *map, *ktot; uint32_t n_union;               // per union site; ktot: an entry per UNI_ROWS sites, scanned in place
+    TextStatus *st;
+    int32_t *o_contig, *o_start, *o_end; uint8_t *o_ctx; int8_t *o_strand; int32_t *o_nsamples, *o_m, *o_u; int64_t n_out;
+};
+struct UniteState;                                                        // mdk_unite.hip: its buffers and what was measured
+
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
     uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
@@ -69,6 +81,7 @@ struct md_text {
     uint8_t **d_ref = nullptr; int64_t *d_ref_len = nullptr;
     long long parse_error_offset = -1;
     uint32_t *d_rsites = nullptr; int64_t *d_rm = nullptr, *d_ru = nullptr; size_t cap_rblocks = 0;      // mdk_regions.hip: its prefix table, apart from d_btot / d_boff
+    UniteState *unite = nullptr;                                      // mdk_unite.hip, made by the first md_text_unite_measure: tables of its own, too
 };
 
 // the block table for nb workgroups
@@ -77,6 +90,8 @@ MDK_HIDDEN int text_blocks_reserve(md_text *t, uint32_t nb);
 MDK_HIDDEN void text_parse_free(md_text *t);
 // ... and mdk_regions.hip
 MDK_HIDDEN void text_regions_free(md_text *t);
+// ... and mdk_unite.hip
+MDK_HIDDEN void text_unite_free(md_text *t);
 
 // one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
 __device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
