@@ -594,6 +594,28 @@ int  md_text_unite_measure(md_text *t, const md_calls_cols *samples, int32_t n_s
 int  md_text_unite_fill(md_text *t, int32_t *contig, int32_t *start, int32_t *end, uint8_t *context, int8_t *strand, int32_t *nsamples,
                         int32_t *nmeth, int32_t *nunmeth, int64_t n_out);
 
+/* ---- two groups compared: Fisher's exact test of two groups of samples, site by site (csrc/mdk_diff.hip, csrc/mdk_diff_core.h) ----
+ * nmeth and nunmeth are two DEVICE matrices of n_samples x n entries, sample-major and contiguous -- row s is sample s, as
+ * md_text_unite_fill writes them --, of int32 (elem_bytes 4) or int64 (elem_bytes 8: sums of md_text_regions stacked); n at most 2^30,
+ * n_samples 1 to 1024.  group holds n_samples DEVICE marks: 0 the sample is in group A, 1 in group B, -1 not used; each group needs a
+ * sample.  Per site i the entries of each group are added in 64 bits into nmeth_a, nunmeth_a, nmeth_b, nunmeth_b (a, b, c, d), and
+ *   meth_diff[i] = 100.0 * (double(c) / double(c + d) - double(a) / double(a + b)), B minus A; 0.0 where a group has no coverage
+ *   pvalue[i]    = the two-sided p-value of Fisher's exact test of the table (a b / c d): the weight of the tables with its margins that
+ *                  are no likelier than it (at most 1 + 1e-7 times as likely: the tie rule of R and scipy) over the weight of all.  1.0
+ *                  where only one table has the margins (a group without coverage is such a site); 0.0 where the table is less than
+ *                  2^-960 as likely as the likeliest, which puts the p-value below 1e-280
+ * by the rule csrc/mdk_diff_core.h states in full: IEEE doubles, a multiplication and a division per table of the support, added in a
+ * fixed order, no lgamma, log or exp -- so the bits are those of a host build of that header (tools/diff_emu), on any device, whatever lane
+ * a site runs on.  MDK_ERR_ARG, with md_dev_last_error naming the condition and the first site that has it, for an entry that is negative,
+ * an entry of 2^26 or more and a pooled margin (a + b, c + d, a + c, b + d) of 2^26 or more; also for a mark other than -1, 0 and 1 and a
+ * group without a sample.  The outputs hold no result then; nothing is written outside them, and the inputs are only read.  One call,
+ * synchronous on the renderer's stream, with the rules of the sections above (one thread at a time, the matrices complete when the call is
+ * made).  It keeps nothing on the renderer and voids nothing: a text, merge, parse or unite measure that waits for its fill stays valid.
+ * Not here: one-sided tests, more than two groups, a model of the replicates' over-dispersion (logistic regression), and any p-value
+ * that needs lgamma. */
+int  md_text_diff(md_text *t, const void *nmeth, const void *nunmeth, int elem_bytes, int32_t n_samples, int64_t n, const int32_t *group,
+                  int64_t *nmeth_a, int64_t *nunmeth_a, int64_t *nmeth_b, int64_t *nunmeth_b, double *meth_diff, double *pvalue);
+
 /* ---- text read back into columns: a bedGraph or a cytosine report parsed on the device (csrc/mdk_parse.hip, csrc/mdk_parse_core.h) ----
  * The way back from md_text_fill: `bytes` bytes of text in DEVICE memory become rows in the layouts above, without the host looking at a line.
  * A line starts at byte 0 and after every '\n' and ends before the next '\n' or at the end of the text; one '\r' before the '\n' is dropped; a

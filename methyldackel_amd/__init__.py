@@ -179,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill",
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill", "md_text_diff",
                "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
@@ -706,6 +706,7 @@ def _text_lib():
                                       C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.md_text_unite_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.md_text_unite_fill.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int64]
+        L.md_text_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_void_p] + [C.c_void_p] * 6
         L.md_text_reference.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.md_text_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
         L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
@@ -1641,6 +1642,119 @@ class Cohort:
         cols = [getattr(self, n).cpu().tolist() for n, _ in SITE_COLUMNS]
         m, u = self.nmeth.t().cpu().tolist(), self.nunmeth.t().cpu().tolist()
         return [(self.contigs[c], a, b, x, s, k) + tuple(zip(mm, uu)) for (c, a, b, x, s, k), mm, uu in zip(zip(*cols), m, u)]
+
+    def diff(self, a, b):
+        """Two groups of the table's samples compared site by site -- what methylKit calls ``calculateDiffMeth``: ``a`` and ``b`` are
+        sequences of sample indices (control and treatment; disjoint, neither empty; the other samples are ignored).  A ``Diff`` with
+        this table's site columns (the same tensors) and, per site, the groups' pooled counts, ``meth_diff`` (percent, b minus a) and
+        ``pvalue``, the two-sided p-value of Fisher's exact test of the pooled 2 x 2 table, made on the device by ``diff_counts``."""
+        out = diff_counts(self.nmeth, self.nunmeth, a, b, _text=self._text)          # (on the table's renderer, if it has one)
+        cols = {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}
+        cols.update(zip((name for name, _ in DIFF_RESULT_COLUMNS), out))
+        return Diff(self.contigs, cols, merged=self.merged)
+
+
+DIFF_SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"))
+DIFF_RESULT_COLUMNS = (("nmeth_a", "int64"), ("nunmeth_a", "int64"), ("nmeth_b", "int64"), ("nunmeth_b", "int64"), ("meth_diff", "float64"), ("pvalue", "float64"))
+
+
+def diff_counts(nmeth, nunmeth, a, b, _text=None):
+    """Two groups of samples compared site by site on the device (csrc/mdk_diff.hip).  ``nmeth`` and ``nunmeth`` are two ``[S, n]``
+    device tensors of one dtype, int32 or int64, contiguous, row s the counts of sample s -- a ``Cohort``'s matrices, or per-sample
+    ``Regions`` sums stacked with ``torch.stack``; ``a`` and ``b`` are sequences of row indices, disjoint, neither empty; rows in
+    neither are ignored.  Returns six new tensors of n entries: ``nmeth_a``, ``nunmeth_a``, ``nmeth_b``, ``nunmeth_b`` (int64: the
+    groups' entries added), ``meth_diff`` (float64: 100 * (b's methylated fraction - a's), 0.0 where a group has no coverage) and
+    ``pvalue`` (float64: Fisher's exact test of the pooled table, two-sided, ties as R and scipy break them; 1.0 where a group has no
+    coverage, 0.0 where it would be below about 1e-280).  The p-value is made of IEEE multiplications, divisions and additions in a
+    fixed order (csrc/mdk_diff_core.h): the same bits on every run and every device, exact to about (4 * support + 8) * 2^-53.  A
+    negative entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do
+    CPU tensors: there is no CPU path.  Not here: one-sided tests, more than two groups, over-dispersion between replicates."""
+    import torch
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"diff_counts: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"diff_counts: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"diff_counts takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    marks = [-1] * S
+    for g, (label, group) in enumerate((("a", a), ("b", b))):
+        group = [group] if isinstance(group, int) else list(group)
+        if not group:
+            raise MdkError(f"diff_counts: group {label} is empty")
+        for i in group:
+            if isinstance(i, bool) or not hasattr(i, "__index__") or not 0 <= int(i) < S:
+                raise MdkError(f"diff_counts: group {label} names sample {i!r}: the matrices hold samples 0 to {S - 1}")
+            i = int(i)
+            if marks[i] == 1 - g:
+                raise MdkError(f"diff_counts: sample {i} is in both groups")
+            marks[i] = g
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not t.is_contiguous():
+            raise MdkError(f"diff_counts: {name} must be contiguous, sample-major")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if t.device.type != "cuda":
+            raise MdkError(f"groups are compared on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    if nunmeth.device != dev:
+        raise MdkError(f"diff_counts: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    L = _text_lib()
+    if _text is None:
+        _text = _TextRenderer(L, dev.index or 0, [])         # this call's own: a stream and a status block, closed when the call returns
+    text = _text
+    group = torch.tensor(marks, dtype=torch.int32, device=dev)
+    out = [torch.empty(n, dtype=getattr(torch, dt), device=dev) for _, dt in DIFF_RESULT_COLUMNS]
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    rc = L.md_text_diff(text.h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, C.c_void_p(group.data_ptr()),
+                        *[C.c_void_p(t.data_ptr()) for t in out])
+    if rc:
+        raise _rc_error("md_text_diff", rc, L.md_dev_last_error().decode())
+    return tuple(out)
+
+
+class Diff(_Columns):
+    """What ``Cohort.diff`` returns, one entry per site of the cohort, on its device: ``contig``, ``start``, ``end`` (int32), ``context``
+    (uint8) and ``strand`` (int8) are the cohort's own tensors; ``nmeth_a``, ``nunmeth_a``, ``nmeth_b``, ``nunmeth_b`` (int64) the
+    groups' pooled counts, ``meth_diff`` (float64) the difference of their methylation in percent, b minus a, ``pvalue`` (float64)
+    Fisher's exact test of the pooled table.  ``contigs`` and ``merged`` are the cohort's.  ``select`` takes a mask, an index or a slice,
+    as for the other results."""
+    COLUMNS = DIFF_SITE_COLUMNS + DIFF_RESULT_COLUMNS
+
+    def __init__(self, contigs, columns, merged=False):
+        super().__init__(contigs, columns)
+        self.merged = bool(merged)
+
+    def qvalue(self):
+        """The p-values of the table's rows adjusted as Benjamini and Hochberg do (R's ``p.adjust(method="BH")``): in descending order of
+        p, ``p * n / rank``, the running minimum, capped at 1.  A float64 tensor on the device, in the rows' order, made with torch:
+        it is a sort, not a hot path.  Rows with equal p-values have the rank of the last of them, so they get equal q-values."""
+        import torch
+        p = self.pvalue
+        n = int(p.shape[0])
+        if not n:
+            return p.clone()
+        ascending, order = torch.sort(p)
+        rank = torch.searchsorted(ascending, ascending, right=True)           # the rows with a p-value at most this one's
+        q = ascending * float(n) / rank.to(torch.float64)
+        q = torch.flip(torch.cummin(torch.flip(q, (0,)), 0).values, (0,)).clamp(max=1.0)
+        out = torch.empty_like(p)
+        out[order] = q
+        return out
+
+    def rows(self):
+        """(chrom, start, end, context, strand, nmeth_a, nunmeth_a, nmeth_b, nunmeth_b, meth_diff, pvalue) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n, _ in self.COLUMNS]
+        return [(self.contigs[r[0]],) + r[1:] for r in zip(*cols)]
+
+    def write(self, path):
+        """the eleven columns, tab-separated, the contig by its name, without a header; formatted on the host, the two doubles with
+        %.17g, which reads back to the same bits.  Returns the path."""
+        with open(path, "w") as f:
+            f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
+        return path
 
 
 def unite(samples, min_samples=None, min_depth=1):

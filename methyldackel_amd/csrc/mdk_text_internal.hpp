@@ -1,5 +1,5 @@
 // mdk_text_internal.hpp -- what the sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows;
-// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals; mdk_unite.hip: samples joined into one site table): the
+// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals; mdk_unite.hip: samples joined into one site table; mdk_diff.hip: two groups of samples compared): the
 // handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
 // scan of the block table.
 #ifndef MDK_TEXT_INTERNAL_HPP
@@ -10,7 +10,7 @@
 #define TEXT_SCAN_WG 1024
 #define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
 
-struct TextStatus { int64_t total; uint32_t err, pad; unsigned long long first; };      // first: mdk_parse.hip, the refused line that starts earliest (offset << 8 | refusal)
+struct TextStatus { int64_t total; uint32_t err, pad; unsigned long long first; };      // first: mdk_parse.hip, the refused line that starts earliest (offset << 8 | refusal); mdk_diff.hip, the first refused site
 // the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
 struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
 struct KText {
@@ -67,6 +67,13 @@ struct KUnite {
     int32_t *o_contig, *o_start, *o_end; uint8_t *o_ctx; int8_t *o_strand; int32_t *o_nsamples, *o_m, *o_u; int64_t n_out;
 };
 struct UniteState;                                                        // mdk_unite.hip: its buffers and what was measured
+
+// two groups of samples compared site by site (mdk_diff.hip): the two count matrices [n_samples, n] of int32 or int64, the samples' marks
+// (0: group A, 1: group B, -1: not used), the six results
+struct KDiff {
+    const void *m, *u; const int32_t *group; int32_t n_samples; int64_t n;
+    int64_t *a, *b, *c, *d; double *diff, *p; TextStatus *st;
+};
 
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
