@@ -616,6 +616,37 @@ int  md_text_unite_fill(md_text *t, int32_t *contig, int32_t *start, int32_t *en
 int  md_text_diff(md_text *t, const void *nmeth, const void *nunmeth, int elem_bytes, int32_t n_samples, int64_t n, const int32_t *group,
                   int64_t *nmeth_a, int64_t *nunmeth_a, int64_t *nmeth_b, int64_t *nunmeth_b, double *meth_diff, double *pvalue);
 
+/* ---- sites joined into regions: significant neighbouring rows of a comparison chained into DMRs (csrc/mdk_dmr.hip, csrc/mdk_dmr_core.h) ----
+ * The n rows (at most 2^30) are DEVICE columns, strictly ascending in (contig, start): contig, start, end (int32), the groups' pooled
+ * counts nmeth_a, nunmeth_a, nmeth_b, nunmeth_b (a, b, c, d: int64, as md_text_diff writes them) and `significant` (uint8; nonzero: the
+ * caller calls the row significant).  context and strand are a comparison's other two columns: they are not read and may be NULL.  No
+ * double of the rows is read.  dir(i) = the sign of c (a + b) - a (c + d), +1 where group B is the more methylated.  A row is a CANDIDATE
+ * if it is significant, a + b > 0, c + d > 0 and dir != 0.  With p the candidate before candidate i, i continues p's region iff
+ * contig[i] == contig[p], dir(i) == dir(p), start[i] - start[p] <= max_gap (bases) and i - p - 1 <= max_skip (rows that are no
+ * candidates between them); otherwise i begins a region, as the first candidate does.  A region runs from its first candidate f to its
+ * last l and reports contig[f], start[f], end[l], nsites = l - f + 1 (every row of the span), nsig (its candidates), direction = dir(f),
+ * the sums of the four counts over ALL rows f .. l, and meth_diff and pvalue of these four sums exactly as md_text_diff gives them.  It is
+ * kept iff nsig >= min_sites, |meth_diff| >= min_diff and the sign of the pooled c (a + b) - a (c + d) is its direction (pooled sums can
+ * reverse the sign of every one of their rows; such a region is dropped).  max_gap >= 0, max_skip >= 0, min_sites >= 1, min_diff finite
+ * and >= 0.  Two steps on a renderer (its stream and its status block; the same rules: synchronous, one thread at a time, the columns
+ * complete when the call is made):
+ *   md_text_dmr_measure  *n_regions = the kept regions.  MDK_ERR_ARG, with md_dev_last_error naming the condition and the first row that
+ *                        has it, for rows not strictly ascending, a contig index outside 0 .. n_contigs - 1, a negative count, a count
+ *                        of 2^26 or more; and, where no row is refused, for a region -- kept or not -- with a pooled margin (a + b, c + d,
+ *                        a + c, b + d) of 2^26 or more, naming the region's first row.  The columns must stay alive until the fill.
+ *                        Temporaries, kept on the renderer until md_text_close: 1 1/8 bytes per row, 56 per 256 rows, 48 per region
+ *                        before the filter;
+ *   md_text_dmr_fill     the twelve columns into DEVICE memory of the caller of n_regions entries each, in ascending order of the
+ *                        regions.  n_regions must be the measured number: a fill without a measure, or with another count, is
+ *                        MDK_ERR_ARG.  The rows a fill reads are the ones the measure chose: columns that changed since give other
+ *                        numbers, never a read outside the n rows or a write outside the outputs.
+ * The tables are this section's own: a text, merge, parse or unite measure that waits for its fill on the same renderer stays valid. */
+int  md_text_dmr_measure(md_text *t, const int32_t *contig, const int32_t *start, const int32_t *end, const uint8_t *context, const int8_t *strand,
+                         const int64_t *nmeth_a, const int64_t *nunmeth_a, const int64_t *nmeth_b, const int64_t *nunmeth_b, const uint8_t *significant,
+                         int64_t n, int32_t n_contigs, int32_t max_gap, int32_t max_skip, int32_t min_sites, double min_diff, int64_t *n_regions);
+int  md_text_dmr_fill(md_text *t, int32_t *contig, int32_t *start, int32_t *end, int32_t *nsites, int32_t *nsig, int8_t *direction,
+                      int64_t *nmeth_a, int64_t *nunmeth_a, int64_t *nmeth_b, int64_t *nunmeth_b, double *meth_diff, double *pvalue, int64_t n_regions);
+
 /* ---- text read back into columns: a bedGraph or a cytosine report parsed on the device (csrc/mdk_parse.hip, csrc/mdk_parse_core.h) ----
  * The way back from md_text_fill: `bytes` bytes of text in DEVICE memory become rows in the layouts above, without the host looking at a line.
  * A line starts at byte 0 and after every '\n' and ends before the next '\n' or at the end of the text; one '\r' before the '\n' is dropped; a

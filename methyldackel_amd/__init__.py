@@ -179,7 +179,7 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
-               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill", "md_text_diff",
+               "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill", "md_text_diff", "md_text_dmr_measure", "md_text_dmr_fill",
                "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
@@ -707,6 +707,8 @@ def _text_lib():
         L.md_text_unite_measure.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.md_text_unite_fill.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int64]
         L.md_text_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_void_p] + [C.c_void_p] * 6
+        L.md_text_dmr_measure.argtypes = [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int64)]
+        L.md_text_dmr_fill.argtypes = [C.c_void_p] + [C.c_void_p] * 12 + [C.c_int64]
         L.md_text_reference.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         L.md_text_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
         L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
@@ -1715,6 +1717,21 @@ def diff_counts(nmeth, nunmeth, a, b, _text=None):
     return tuple(out)
 
 
+def _benjamini_hochberg(p):
+    """what ``Diff.qvalue`` and ``Dmrs.qvalue`` return for the p-values ``p``: a new tensor beside it, in its order"""
+    import torch
+    n = int(p.shape[0])
+    if not n:
+        return p.clone()
+    ascending, order = torch.sort(p)
+    rank = torch.searchsorted(ascending, ascending, right=True)           # the rows with a p-value at most this one's
+    q = ascending * float(n) / rank.to(torch.float64)
+    q = torch.flip(torch.cummin(torch.flip(q, (0,)), 0).values, (0,)).clamp(max=1.0)
+    out = torch.empty_like(p)
+    out[order] = q
+    return out
+
+
 class Diff(_Columns):
     """What ``Cohort.diff`` returns, one entry per site of the cohort, on its device: ``contig``, ``start``, ``end`` (int32), ``context``
     (uint8) and ``strand`` (int8) are the cohort's own tensors; ``nmeth_a``, ``nunmeth_a``, ``nmeth_b``, ``nunmeth_b`` (int64) the
@@ -1731,18 +1748,66 @@ class Diff(_Columns):
         """The p-values of the table's rows adjusted as Benjamini and Hochberg do (R's ``p.adjust(method="BH")``): in descending order of
         p, ``p * n / rank``, the running minimum, capped at 1.  A float64 tensor on the device, in the rows' order, made with torch:
         it is a sort, not a hot path.  Rows with equal p-values have the rank of the last of them, so they get equal q-values."""
+        return _benjamini_hochberg(self.pvalue)
+
+    def dmrs(self, significant, max_gap=300, max_skip=0, min_sites=3, min_diff=0.0):
+        """Significant neighbouring rows joined into differentially methylated regions on the rows' device (csrc/mdk_dmr.hip; the rule
+        in full: csrc/mdk_dmr_core.h) -- what DSS ``callDMR`` and metilene report.  ``significant`` is a ``torch.bool`` tensor of one
+        entry per row on the rows' device, for example ``d.qvalue() < 0.01``.  A row is a candidate if it is significant, both groups
+        cover it and their fractions differ; its direction is the sign of b's fraction minus a's, from the four counts alone.  A
+        candidate continues the region of the candidate before it if both are on one contig and of one direction, their starts at
+        most ``max_gap`` bases apart and at most ``max_skip`` rows that are no candidates between them; otherwise it begins a region.
+        A region reports its span, ``nsites`` (every row of the span), ``nsig`` (its candidates), ``direction``, the four counts added
+        over ALL rows of the span, and ``meth_diff`` and ``pvalue`` of these sums, bit for bit what ``diff_counts`` gives for them.
+        It is kept if ``nsig >= min_sites``, ``abs(meth_diff) >= min_diff`` (percent) and the pooled difference has the direction of
+        its rows (pooling can reverse it: such a region is dropped).  Returns a ``Dmrs``, ascending.  The defaults are conventions,
+        not measurements: 300 bases is metilene's distance, three sites DSS's minimum.  Rows not strictly ascending in (contig,
+        start), a contig index outside ``contigs``, a negative count, a count of 2^26 or more and a region whose pooled margins reach
+        2^26 raise MdkError (rc -3) naming the first such row; so do CPU tensors: there is no CPU path.  Not here: smoothing, a
+        minimum length in bases (``select((r.end - r.start) >= L)`` does it), merging regions of opposite direction."""
+        import math
         import torch
-        p = self.pvalue
-        n = int(p.shape[0])
+        names = [n for n, _ in DIFF_SITE_COLUMNS[:3] + DIFF_RESULT_COLUMNS[:4]]
+        cols = [getattr(self, n) for n in names]
+        n = len(self)
+        for what, v, low in (("max_gap", max_gap, 0), ("max_skip", max_skip, 0), ("min_sites", min_sites, 1)):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not low <= int(v) <= 2 ** 31 - 1:
+                raise MdkError(f"dmrs: {what} must be an integer between {low} and 2^31 - 1, not {v!r}")
+        if isinstance(min_diff, bool) or not isinstance(min_diff, (int, float)) or not math.isfinite(min_diff) or min_diff < 0:
+            raise MdkError(f"dmrs: min_diff must be a finite number of percent, 0 or more, not {min_diff!r}")
+        if not isinstance(significant, torch.Tensor) or significant.dtype != torch.bool:
+            raise MdkError("dmrs: significant must be a torch.bool tensor with one entry per row, such as d.qvalue() < 0.01")
+        if significant.dim() != 1 or significant.shape[0] != n:
+            raise MdkError(f"dmrs: significant has the shape {tuple(significant.shape)}: one entry per row, ({n},)")
+        for t, name in zip(cols + [significant], names + ["significant"]):
+            if t.device.type != "cuda":
+                raise MdkError(f"regions are joined on the device: {'the ' + name + ' column' if name != 'significant' else name} is a {t.device.type} tensor, and there is no CPU path")
+        dev = cols[0].device
+        if significant.device != dev:
+            raise MdkError(f"dmrs: significant is on {significant.device}, the rows on {dev}")
+        for t, name, (_, dt) in zip(cols, names, DIFF_SITE_COLUMNS[:3] + DIFF_RESULT_COLUMNS[:4]):
+            if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+                raise MdkError(f"dmrs: the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        if not significant.is_contiguous():
+            raise MdkError("dmrs: significant must be contiguous")
+        if n > 1 << 30:
+            raise MdkError(f"{n} rows: more than 2^30")
         if not n:
-            return p.clone()
-        ascending, order = torch.sort(p)
-        rank = torch.searchsorted(ascending, ascending, right=True)           # the rows with a p-value at most this one's
-        q = ascending * float(n) / rank.to(torch.float64)
-        q = torch.flip(torch.cummin(torch.flip(q, (0,)), 0).values, (0,)).clamp(max=1.0)
-        out = torch.empty_like(p)
-        out[order] = q
-        return out
+            return Dmrs(list(self.contigs), {name: torch.empty(0, dtype=getattr(torch, dt), device=dev) for name, dt in DMR_COLUMNS}, merged=self.merged)
+        L = self._renderer(dev)
+        mask = significant.view(torch.uint8)                     # (a bool tensor holds a byte of 0 or 1 per entry)
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        p = [C.c_void_p(t.data_ptr()) for t in cols]
+        count = C.c_int64()
+        rc = L.md_text_dmr_measure(self._text.h, p[0], p[1], p[2], None, None, p[3], p[4], p[5], p[6], C.c_void_p(mask.data_ptr()), n, len(self.contigs),
+                                   int(max_gap), int(max_skip), int(min_sites), float(min_diff), C.byref(count))
+        if rc:
+            raise _rc_error("md_text_dmr_measure", rc, L.md_dev_last_error().decode())
+        out = {name: torch.empty(count.value, dtype=getattr(torch, dt), device=dev) for name, dt in DMR_COLUMNS}
+        rc = L.md_text_dmr_fill(self._text.h, *[C.c_void_p(out[name].data_ptr()) for name, _ in DMR_COLUMNS], count.value)
+        if rc:
+            raise _rc_error("md_text_dmr_fill", rc, L.md_dev_last_error().decode())
+        return Dmrs(list(self.contigs), out, merged=self.merged)
 
     def rows(self):
         """(chrom, start, end, context, strand, nmeth_a, nunmeth_a, nmeth_b, nunmeth_b, meth_diff, pvalue) tuples on the host"""
@@ -1754,6 +1819,45 @@ class Diff(_Columns):
         %.17g, which reads back to the same bits.  Returns the path."""
         with open(path, "w") as f:
             f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
+        return path
+
+
+DMR_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("nsites", "int32"), ("nsig", "int32"), ("direction", "int8"),
+               ("nmeth_a", "int64"), ("nunmeth_a", "int64"), ("nmeth_b", "int64"), ("nunmeth_b", "int64"), ("meth_diff", "float64"), ("pvalue", "float64"))
+
+
+class Dmrs(_Columns):
+    """What ``Diff.dmrs`` returns, one entry per region, ascending, on the rows' device: ``contig``, ``start``, ``end`` (int32: from
+    the start of the region's first significant row to the end of its last), ``nsites`` (int32: the rows of the span, significant or
+    not), ``nsig`` (int32: the significant rows that made it), ``direction`` (int8: +1 where group b is the more methylated, -1 where
+    a is), ``nmeth_a``, ``nunmeth_a``, ``nmeth_b``, ``nunmeth_b`` (int64: the groups' counts added over every row of the span),
+    ``meth_diff`` and ``pvalue`` (float64: of these sums, as ``diff_counts`` gives them).  ``contigs`` and ``merged`` are the rows'.
+    ``select`` takes a mask, an index or a slice, as for the other results."""
+    COLUMNS = DMR_COLUMNS
+
+    def __init__(self, contigs, columns, merged=False):
+        super().__init__(contigs, columns)
+        self.merged = bool(merged)
+
+    def qvalue(self):
+        """the regions' p-values adjusted as Benjamini and Hochberg do, over the regions of this table: ``Diff.qvalue``'s rule"""
+        return _benjamini_hochberg(self.pvalue)
+
+    def intervals(self):
+        """the regions as an ``Intervals`` on their device (the same three tensors): ``calls.regions(dmrs.intervals())`` gives a
+        sample's own sums over the regions -- a row belongs to the region that holds its start, so every row of a span is counted"""
+        return Intervals(self.contigs, self.contig, self.start, self.end)
+
+    def rows(self):
+        """(chrom, start, end, nsites, nsig, direction, nmeth_a, nunmeth_a, nmeth_b, nunmeth_b, meth_diff, pvalue) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n, _ in DMR_COLUMNS]
+        return [(self.contigs[r[0]],) + r[1:] for r in zip(*cols)]
+
+    def write(self, path):
+        """the twelve columns, tab-separated, the contig by its name, without a header; formatted on the host, the two doubles with
+        %.17g, which reads back to the same bits.  Returns the path."""
+        with open(path, "w") as f:
+            f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
         return path
 
 

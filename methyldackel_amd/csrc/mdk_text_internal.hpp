@@ -1,5 +1,5 @@
 // mdk_text_internal.hpp -- what the sources behind a md_text handle share (mdk_text.hip: the text; mdk_merge.hip: mergeContext's rows;
-// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals; mdk_unite.hip: samples joined into one site table; mdk_diff.hip: two groups of samples compared): the
+// mdk_parse.hip: text read back into columns; mdk_regions.hip: sums over intervals; mdk_unite.hip: samples joined into one site table; mdk_diff.hip: two groups of samples compared; mdk_dmr.hip: significant sites joined into regions): the
 // handle itself -- its stream, the name table, the table of one entry per 256 rows, the status block --, the kernels' argument blocks and the
 // scan of the block table.
 #ifndef MDK_TEXT_INTERNAL_HPP
@@ -10,7 +10,7 @@
 #define TEXT_SCAN_WG 1024
 #define TEXT_MAX_ROWS (1ll << 30)         // rows of one measure / fill
 
-struct TextStatus { int64_t total; uint32_t err, pad; unsigned long long first; };      // first: mdk_parse.hip, the refused line that starts earliest (offset << 8 | refusal); mdk_diff.hip, the first refused site
+struct TextStatus { int64_t total; uint32_t err, pad; unsigned long long first; };      // first: mdk_parse.hip, the refused line that starts earliest (offset << 8 | refusal); mdk_diff.hip, the first refused site; mdk_dmr.hip, the first refused row
 // the columns of either layout: a = start (calls) or pos (cytosines), b = end (calls only), tri = trinucleotide (cytosines only)
 struct TextView { const int32_t *contig, *a, *b, *m, *u; const uint8_t *ctx; const int8_t *strand; const uint8_t *tri; };
 struct KText {
@@ -75,6 +75,21 @@ struct KDiff {
     int64_t *a, *b, *c, *d; double *diff, *p; TextStatus *st;
 };
 
+// significant neighbouring sites joined into regions (mdk_dmr.hip): the rows and the parameters; the tables per row, per block of 256 rows
+// and per raw region (all mdk_dmr.hip's own); the result
+struct KDmr {
+    const int32_t *contig, *start, *end; const int64_t *a, *b, *c, *d; const uint8_t *sig;
+    uint32_t n; int32_t n_contigs, max_gap, max_skip, min_sites; double min_diff;
+    uint8_t *code; unsigned long long *hmask;                             // per row: DMR_CODE_*; per wavefront of rows: its heads as a mask
+    int32_t *blast; uint32_t *bcand; int64_t *ba, *bb, *bc, *bd;          // nb + 1 entries each, scanned in place: the last candidate before the block (entry nb: of all), candidates and counts before it
+    uint32_t *htot; int64_t *hoff;                                        // the blocks' heads, and the raw regions before each block
+    uint32_t n_raw; int32_t *first, *last, *rnsig; uint32_t *rpos; int64_t *ra, *rb, *rc, *rd;      // per raw region; rpos: its place among the kept of its 256, or DMR_NO_PLACE
+    uint32_t *ktot; int64_t *koff;                                        // per 256 raw regions: the kept, and the kept before them
+    TextStatus *st;
+    int32_t *o_contig, *o_start, *o_end, *o_nsites, *o_nsig; int8_t *o_dir; int64_t *o_a, *o_b, *o_c, *o_d; double *o_diff, *o_p; int64_t n_out;
+};
+struct DmrState;                                                          // mdk_dmr.hip: its buffers and what was measured
+
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
     uint32_t *d_name_off = nullptr; uint8_t *d_names = nullptr;
@@ -89,6 +104,7 @@ struct md_text {
     long long parse_error_offset = -1;
     uint32_t *d_rsites = nullptr; int64_t *d_rm = nullptr, *d_ru = nullptr; size_t cap_rblocks = 0;      // mdk_regions.hip: its prefix table, apart from d_btot / d_boff
     UniteState *unite = nullptr;                                      // mdk_unite.hip, made by the first md_text_unite_measure: tables of its own, too
+    DmrState *dmr = nullptr;                                          // mdk_dmr.hip, made by the first md_text_dmr_measure: likewise
 };
 
 // the block table for nb workgroups
@@ -99,6 +115,8 @@ MDK_HIDDEN void text_parse_free(md_text *t);
 MDK_HIDDEN void text_regions_free(md_text *t);
 // ... and mdk_unite.hip
 MDK_HIDDEN void text_unite_free(md_text *t);
+// ... and mdk_dmr.hip
+MDK_HIDDEN void text_dmr_free(md_text *t);
 
 // one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
 __device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
