@@ -12,8 +12,8 @@ all: $(B)/libmdk_hip.so $(B)/libmdk_extract.so $(B)/MethylDackel tools oracle
 
 # -fgpu-rdc: the sources become ONE code object; the runtime loads a code object at the first use of one of its kernels and each load
 # costs the command ~30 ms of start-up (three of them did: pileup, preparation, inflate)
-HIPSRC := methyldackel_amd/csrc/mdk_hip.hip methyldackel_amd/csrc/mdk_comm.hip methyldackel_amd/csrc/mdk_prep.hip methyldackel_amd/csrc/mdk_inflate.hip methyldackel_amd/csrc/mdk_calls.hip methyldackel_amd/csrc/mdk_reads.hip methyldackel_amd/csrc/mdk_bias.hip methyldackel_amd/csrc/mdk_cytosines.hip methyldackel_amd/csrc/mdk_text.hip methyldackel_amd/csrc/mdk_merge.hip methyldackel_amd/csrc/mdk_parse.hip methyldackel_amd/csrc/mdk_regions.hip methyldackel_amd/csrc/mdk_unite.hip methyldackel_amd/csrc/mdk_diff.hip methyldackel_amd/csrc/mdk_dmr.hip
-$(B)/libmdk_hip.so: $(HIPSRC) methyldackel_amd/csrc/mdk_hip_internal.hpp methyldackel_amd/csrc/mdk_overlap_rule.h methyldackel_amd/csrc/mdk_pair_rule.h methyldackel_amd/csrc/mdk_inflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_text_internal.hpp methyldackel_amd/csrc/mdk_merge_core.h methyldackel_amd/csrc/mdk_parse_core.h methyldackel_amd/csrc/mdk_region_core.h methyldackel_amd/csrc/mdk_unite_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_dmr_core.h include/mdk_hip.h
+HIPSRC := methyldackel_amd/csrc/mdk_hip.hip methyldackel_amd/csrc/mdk_comm.hip methyldackel_amd/csrc/mdk_prep.hip methyldackel_amd/csrc/mdk_inflate.hip methyldackel_amd/csrc/mdk_calls.hip methyldackel_amd/csrc/mdk_reads.hip methyldackel_amd/csrc/mdk_bias.hip methyldackel_amd/csrc/mdk_cytosines.hip methyldackel_amd/csrc/mdk_text.hip methyldackel_amd/csrc/mdk_merge.hip methyldackel_amd/csrc/mdk_parse.hip methyldackel_amd/csrc/mdk_regions.hip methyldackel_amd/csrc/mdk_unite.hip methyldackel_amd/csrc/mdk_diff.hip methyldackel_amd/csrc/mdk_dmr.hip methyldackel_amd/csrc/mdk_deflate.hip
+$(B)/libmdk_hip.so: $(HIPSRC) methyldackel_amd/csrc/mdk_hip_internal.hpp methyldackel_amd/csrc/mdk_overlap_rule.h methyldackel_amd/csrc/mdk_pair_rule.h methyldackel_amd/csrc/mdk_inflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_text_internal.hpp methyldackel_amd/csrc/mdk_merge_core.h methyldackel_amd/csrc/mdk_parse_core.h methyldackel_amd/csrc/mdk_region_core.h methyldackel_amd/csrc/mdk_unite_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_dmr_core.h methyldackel_amd/csrc/mdk_deflate_core.h include/mdk_hip.h
 	@mkdir -p $(B)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fgpu-rdc $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ $(HIPSRC) -ldl
 
@@ -23,7 +23,7 @@ $(B)/libmdk_extract.so: $(HOSTSRC) methyldackel_amd/csrc/host/mdk_io.h methyldac
 $(B)/MethylDackel: methyldackel_amd/csrc/host/main.c $(B)/libmdk_extract.so
 	$(CC) $(CFLAGS) -Iinclude -o $@ methyldackel_amd/csrc/host/main.c -L$(B) -lmdk_extract -lmdk_hip -Wl,-rpath,'$$ORIGIN' -lz -lm
 
-tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/dmr_emu tools/_build/diff_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
+tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/dmr_emu tools/_build/diff_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
 	@mkdir -p tools/_build
 	$(CC) -O2 -g -Wall -shared -fPIC -Iinclude -o $@ tools/piece_standin.c -lz
@@ -51,6 +51,9 @@ tools/_build/parse_emu: tools/parse_emu.cpp methyldackel_amd/csrc/mdk_parse_core
 tools/_build/region_emu: tools/region_emu.cpp methyldackel_amd/csrc/mdk_region_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/region_emu.cpp -Imethyldackel_amd/csrc
+tools/_build/deflate_emu: tools/deflate_emu.cpp methyldackel_amd/csrc/mdk_deflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h
+	@mkdir -p tools/_build
+	g++ -O2 -Wall -o $@ tools/deflate_emu.cpp -Imethyldackel_amd/csrc
 tools/_build/unite_emu: tools/unite_emu.cpp methyldackel_amd/csrc/mdk_unite_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/unite_emu.cpp -Imethyldackel_amd/csrc

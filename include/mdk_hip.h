@@ -227,6 +227,8 @@ int  md_piece_wait(md_piece *p, md_piece_info *info);
 /* inflated bytes / record offsets copied back to the host (tests; files whose records straddle members) */
 int  md_piece_read(md_piece *p, uint64_t off, uint64_t bytes, uint8_t *dst);
 int  md_piece_read_records(md_piece *p, uint32_t first, uint32_t n, uint32_t *dst);
+/* inflated bytes copied to other DEVICE memory (text files read back: the bytes are parsed on the device, md_text_parse_*) */
+int  md_piece_copy(md_piece *p, uint64_t off, uint64_t bytes, void *d_dst);
 /* the kernels alone, re-run on the resident piece and timed with HIP events on its stream */
 int  md_piece_bench(md_piece *p, int iters, float *ms_inflate, float *ms_walk);
 int  md_piece_bench_crc(md_piece *p, int iters, float *ms_crc);      /* k_crc32 alone on the resident piece (and its verdict) */
@@ -682,6 +684,20 @@ int  md_text_parse_measure(md_text *t, const uint8_t *text, int64_t bytes, int f
 int  md_text_parse_fill_calls(md_text *t, const md_calls_cols *dst, int64_t rows);
 int  md_text_parse_fill_cytosines(md_text *t, const md_cytosines_cols *dst, int64_t rows);
 int64_t md_text_parse_error_offset(const md_text *t);
+
+/* BGZF made on the device (csrc/mdk_deflate.hip, csrc/mdk_deflate_core.h): `n` bytes of DEVICE memory -- the text md_text_fill left there, or any
+ * bytes -- compressed into complete BGZF members in device memory, so that a block of text crosses to the host once and compressed.  Member i holds
+ * input bytes [65280 i, min(65280 (i + 1), n)), bgzip's cut: the 18-byte header (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, "BC", BSIZE), one raw
+ * RFC 1951 stream ending in a final block -- LZ77 matches (4 to 258 bytes, up to 32768 back) and Huffman codes fitted to the member (a dynamic block), or
+ * a stored block where that is no larger --, CRC32 and ISIZE.  No member is longer than 65536 bytes or than its stored form, 18 + 5 + input + 8 bytes.
+ * The bytes are a function of the input alone (tools/deflate_emu.cpp makes the same ones on the host); gzip, zcat, bgzip, tabix and R read them.
+ * There are no compression levels.  Synchronous on the renderer's stream, one thread at a time, as the calls above:
+ *   md_text_deflate_measure   compresses (n at most 2^31 - 1; the input must be complete when the call is made) and gives *out_bytes: the members'
+ *                             lengths added up, plus the 28-byte EOF member if `eof` is not 0.  n == 0 gives the EOF member alone, or nothing;
+ *   md_text_deflate_fill      the members back to back, then the EOF member, into DEVICE memory of exactly out_bytes bytes (any alignment).
+ * The compressed members wait in memory of the renderer's between the two calls, 64 KiB per member, kept for the next call. */
+int  md_text_deflate_measure(md_text *t, const uint8_t *d_in, int64_t n, int eof, int64_t *out_bytes);
+int  md_text_deflate_fill(md_text *t, void *d_out, int64_t out_bytes);
 
 /* An idle handle (nothing uploaded or launched that has not been collected) back to the state md_dev_open left it in, with `cfg`
  * (same n_slots and n_streams): contigs, -l runs, mappability tracks, the preparation settings, the mbias histogram, the calls and reads state

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 import subprocess
 from pathlib import Path
 
@@ -175,12 +176,12 @@ HIP_SYMBOLS = ["md_dev_count", "md_dev_warm", "md_dev_quiesce", "md_dev_reserve_
                "md_dev_mbias_submit", "md_dev_mbias_submit_raw", "md_dev_mbias_read", "md_dev_mbias_reset", "md_dev_slot_sync",
                "md_dev_mbias_group", "md_dev_mbias_collect", "md_dev_mbias_redone", "md_dev_bias_finish", "md_bias_set_count", "md_bias_set_len", "md_bias_set_redone", "md_bias_set_hist", "md_bias_set_copy", "md_bias_set_free",
                "md_dev_perread_submit", "md_dev_perread_download", "md_dev_perread_submit_raw", "md_dev_perread_download_raw", "md_dev_read_raw",
-               "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_bench", "md_piece_bench_crc",
+               "md_piece_members_per_round", "md_piece_create", "md_piece_destroy", "md_piece_submit", "md_piece_wait", "md_piece_read", "md_piece_read_records", "md_piece_copy", "md_piece_bench", "md_piece_bench_crc",
                "md_dev_calls_begin", "md_dev_calls_group", "md_dev_calls_finish", "md_calls_set_count", "md_calls_set_copy", "md_calls_set_free", "md_dev_reset",
                "md_dev_reads_begin", "md_dev_reads_slot", "md_dev_reads_collect", "md_dev_reads_host", "md_dev_reads_finish", "md_reads_set_count", "md_reads_set_name_bytes", "md_reads_set_copy", "md_reads_set_free",
                "md_dev_cytosines_begin", "md_dev_cytosines_group", "md_dev_cytosines_finish", "md_cytosines_set_count", "md_cytosines_set_copy", "md_cytosines_set_free",
                "md_text_open", "md_text_measure_calls", "md_text_measure_cytosines", "md_text_measure_reads", "md_text_fill", "md_text_gather_names", "md_text_close", "md_text_merge_measure", "md_text_merge_fill", "md_text_regions", "md_text_unite_measure", "md_text_unite_fill", "md_text_diff", "md_text_dmr_measure", "md_text_dmr_fill",
-               "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset"]
+               "md_text_reference", "md_text_parse_measure", "md_text_parse_fill_calls", "md_text_parse_fill_cytosines", "md_text_parse_error_offset", "md_text_deflate_measure", "md_text_deflate_fill"]
 EXTRACT_SYMBOLS = ["extract_main", "mdk_plan_open", "mdk_plan_close", "mdk_plan_dev_cfg", "mdk_plan_ensure_reference",
                    "mdk_plan_next_chunk", "mdk_plan_try_next_chunk", "mdk_plan_emit", "mdk_plan_finish", "mdk_plan_set_shard", "mdk_plan_n_targets", "mdk_plan_target_name",
                    "mdk_plan_target_len", "mdk_plan_regions", "mdk_plan_set_prep", "mdk_plan_set_hold", "mdk_plan_prep_cfg", "mdk_plan_host_prepare",
@@ -269,6 +270,7 @@ def lib_hip():
         L.md_piece_wait.argtypes = [C.c_void_p, C.POINTER(md_piece_info)]
         L.md_piece_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.md_piece_read_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.md_piece_copy.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         L.md_piece_bench.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.md_dev_perread_download_raw.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(md_pr_count)), C.POINTER(C.c_int64)]
         L.md_host_alloc.restype = C.c_void_p
@@ -714,6 +716,8 @@ def _text_lib():
         L.md_text_parse_fill_calls.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
         L.md_text_parse_fill_cytosines.argtypes = [C.c_void_p, C.POINTER(md_text_cols), C.c_int64]
         L.md_text_parse_error_offset.argtypes = [C.c_void_p]; L.md_text_parse_error_offset.restype = C.c_int64
+        L.md_text_deflate_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]
+        L.md_text_deflate_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L._text_types = True
     return L
 
@@ -764,6 +768,46 @@ def _session_lib():
         L.mdk_bias_free.argtypes = [C.c_void_p]
         L._session_types = True
     return L
+
+
+# ---- BGZF made on the device (include/mdk_hip.h md_text_deflate_*, csrc/mdk_deflate.hip) ----
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BGZF_MEMBER = 65280                                           # input bytes of a member: bgzip's cut
+_BGZF_RENDERERS = {}                                          # device index -> the md_text `bgzf_compress` works on
+
+
+def _deflate(L, text, data, eof):
+    """``data`` (a contiguous uint8 tensor on the renderer's device) as BGZF members on that device, the EOF member behind them if asked for"""
+    import torch
+    torch.cuda.current_stream(data.device).synchronize()         # the bytes are complete, and nothing of torch's is queued on memory it hands out next
+    size = C.c_int64()
+    rc = L.md_text_deflate_measure(text.h, C.c_void_p(data.data_ptr() if data.numel() else 0), data.numel(), int(bool(eof)), C.byref(size))
+    if rc:
+        raise _rc_error("md_text_deflate_measure", rc, L.md_dev_last_error().decode())
+    out = torch.empty(size.value, dtype=torch.uint8, device=data.device)
+    rc = L.md_text_deflate_fill(text.h, C.c_void_p(out.data_ptr() if size.value else 0), size.value)
+    if rc:
+        raise _rc_error("md_text_deflate_fill", rc, L.md_dev_last_error().decode())
+    return out
+
+
+def bgzf_compress(data, eof=True):
+    """``data``, a contiguous uint8 tensor on a device, as a BGZF file's bytes on that device (csrc/mdk_deflate.hip): members of 65280 input
+    bytes, bgzip's cut, each compressed by one wavefront with LZ77 matches and Huffman codes fitted to it (stored where that is smaller:
+    no member is longer than its input plus 31 bytes), then the 28-byte EOF member unless ``eof`` is false.  No bytes give the EOF member
+    alone.  ``gzip.decompress`` of the result is ``data``; the bytes depend on ``data`` alone.  There are no compression levels.  A CPU
+    tensor raises MdkError: there is no CPU path."""
+    import torch
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise MdkError("bgzf_compress needs a contiguous one-dimensional uint8 tensor")
+    if data.device.type != "cuda":
+        raise MdkError(f"bytes are compressed on the device: the tensor is a {data.device.type} tensor, and there is no CPU path")
+    if data.numel() > (1 << 31) - 1:
+        raise MdkError("bgzf_compress takes at most 2^31 - 1 bytes a call")
+    L, k = _text_lib(), data.device.index or 0
+    if k not in _BGZF_RENDERERS:
+        _BGZF_RENDERERS[k] = _TextRenderer(L, k, [])
+    return _deflate(L, _BGZF_RENDERERS[k], data, eof)
 
 
 class _Columns:
@@ -923,18 +967,37 @@ class _Columns:
                 raise _rc_error("md_text_fill", rc, L.md_dev_last_error().decode())
             yield out
 
-    def _render(self, fmt, context, head, block_rows):
+    def _compressed(self, blocks, head, dev):
+        """the header line and every block of text as BGZF members on the device (a member never spans two blocks; the header's are its own)"""
         import torch
-        parts = [b for b in self._text_blocks(fmt, context, block_rows) if b.numel()]
+        L = _text_lib()
+        if head:
+            yield _deflate(L, self._text, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev), False)
+        for b in blocks:
+            if b.numel():
+                yield _deflate(L, self._text, b, False)
+
+    def _render(self, fmt, context, head, block_rows, compress=False):
+        import torch
+        blocks = self._text_blocks(fmt, context, block_rows)
         dev = getattr(self, self.COLUMNS[0][0]).device
+        if compress:
+            parts = list(self._compressed(blocks, head, dev)) + [torch.frombuffer(bytearray(BGZF_EOF), dtype=torch.uint8).to(dev)]
+            return torch.cat(parts) if len(parts) > 1 else parts[0]
+        parts = [b for b in blocks if b.numel()]
         if head:
             parts.insert(0, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
         return torch.cat(parts) if len(parts) > 1 else parts[0] if parts else torch.empty(0, dtype=torch.uint8, device=dev)
 
-    def _write_file(self, path, fmt, context, head, block_rows):
-        """the header, then every block of text: one device-to-host copy into a pinned buffer each, appended to the file"""
+    def _write_file(self, path, fmt, context, head, block_rows, compress=False):
+        """the header, then every block of text: one device-to-host copy into a pinned buffer each, appended to the file.  ``compress``: the
+        header and every block are BGZF members by then (k_deflate), and one EOF member ends the file"""
         import torch
         pin, blocks = None, self._text_blocks(fmt, context, block_rows)
+        if compress:
+            blocks, head, tail = self._compressed(blocks, head, getattr(self, self.COLUMNS[0][0]).device), b"", BGZF_EOF
+        else:
+            tail = b""
         with open(path, "wb") as f:
             f.write(head)
             for b in blocks:
@@ -946,6 +1009,7 @@ class _Columns:
                 pin[:n].copy_(b, non_blocking=True)
                 torch.cuda.current_stream(b.device).synchronize()
                 f.write(memoryview(pin.numpy())[:n])
+            f.write(tail)
         return path
 
 
@@ -1090,29 +1154,190 @@ def _parse_line_number(path, offset):
     return n
 
 
-def _parse_file(L, text, path, fmt, columns, dev, block_bytes):
-    """the columns of one file, a list of dicts (one per piece), parsed on ``dev`` by k_parse_len / k_parse_fill"""
+def _parse_text(L, text, d, n, path, at, fmt, columns, dev, line_number):
+    """the columns of the ``n`` bytes of text at the start of the device tensor ``d`` (the file's decompressed bytes from ``at``)"""
     import torch
     fill = L.md_text_parse_fill_cytosines if fmt == PARSE_CYTOSINE_REPORT else L.md_text_parse_fill_calls
+    rows = C.c_int64()
+    rc = L.md_text_parse_measure(text.h, C.c_void_p(d.data_ptr()), n, fmt, C.byref(rows))
+    if rc:
+        raise _rc_error("md_text_parse_measure", rc, L.md_dev_last_error().decode())
+    cols = {name: torch.empty(rows.value * (3 if name == "trinucleotide" else 1), dtype=getattr(torch, dt), device=dev) for name, dt in columns}
+    rc = fill(text.h, C.byref(md_text_cols(*[C.c_void_p(cols[name].data_ptr()) for name, _ in columns])), rows.value)
+    if rc:
+        detail, off = L.md_dev_last_error().decode(), int(L.md_text_parse_error_offset(text.h))
+        if off >= 0:
+            detail = f"{path}, line {line_number(path, at + off)}: {detail}"
+        else:
+            detail = f"{path}: {detail}"
+        raise _rc_error("reading", rc, detail)
+    return cols
+
+
+def _parse_file(L, text, path, fmt, columns, dev, block_bytes):
+    """the columns of one file, a list of dicts (one per piece), parsed on ``dev`` by k_parse_len / k_parse_fill.  A file that begins with
+    the gzip magic is a BGZF file or refused (``_gz_kind``): its members are inflated on the device and parsed where they lie"""
+    import torch
+    kind = _gz_kind(path)
+    if kind == "gzip":
+        raise MdkError(f"{path}: a gzip file that is not BGZF (no BC subfield in its header): one member of any length is one wavefront's work. "
+                       "Recompress it with bgzip (zcat file.gz | bgzip > file.bgz.gz), or decompress it")
+    if kind == "bgzf":
+        return _parse_bgzf(L, text, path, fmt, columns, dev, block_bytes)
     out = []
     for pin, n, at in _parse_pieces(path, block_bytes):
         d = torch.empty(n, dtype=torch.uint8, device=dev)
         d.copy_(pin[:n], non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()             # the text is complete, and the pinned buffer may take the next piece
-        rows = C.c_int64()
-        rc = L.md_text_parse_measure(text.h, C.c_void_p(d.data_ptr()), n, fmt, C.byref(rows))
-        if rc:
-            raise _rc_error("md_text_parse_measure", rc, L.md_dev_last_error().decode())
-        cols = {name: torch.empty(rows.value * (3 if name == "trinucleotide" else 1), dtype=getattr(torch, dt), device=dev) for name, dt in columns}
-        rc = fill(text.h, C.byref(md_text_cols(*[C.c_void_p(cols[name].data_ptr()) for name, _ in columns])), rows.value)
-        if rc:
-            detail, off = L.md_dev_last_error().decode(), int(L.md_text_parse_error_offset(text.h))
-            if off >= 0:
-                detail = f"{path}, line {_parse_line_number(path, at + off)}: {detail}"
-            else:
-                detail = f"{path}: {detail}"
-            raise _rc_error("reading", rc, detail)
-        out.append(cols)
+        out.append(_parse_text(L, text, d, n, path, at, fmt, columns, dev, _parse_line_number))
+    return out
+
+
+# ---- BGZF files read back (csrc/mdk_inflate.hip md_piece_*: the members are inflated and CRC32-checked on the device) ----
+def _bgzf_bsize(buf, o, end):
+    """the length of the BGZF member whose header stands at ``buf[o]`` -- the gzip magic, deflate, FLG = FEXTRA alone and a BC subfield of
+    two bytes, which is BSIZE -- or 0: no such header there (or not all of it before ``end``)"""
+    if o + 12 > end or buf[o] != 0x1f or buf[o + 1] != 0x8b or buf[o + 2] != 8 or buf[o + 3] != 4:
+        return 0
+    x, xe = o + 12, o + 12 + (buf[o + 10] | buf[o + 11] << 8)
+    if xe > end:
+        return 0
+    while x + 4 <= xe:
+        slen = buf[x + 2] | buf[x + 3] << 8
+        if buf[x] == 66 and buf[x + 1] == 67 and slen == 2 and x + 6 <= xe:
+            return (buf[x + 4] | buf[x + 5] << 8) + 1
+        x += 4 + slen
+    return 0
+
+
+def _gz_kind(path):
+    """what a file is by its content, not its name: "plain" (no gzip magic), "bgzf" (a BGZF header first) or "gzip" (any other gzip file)"""
+    with open(path, "rb") as f:
+        h = f.read(12 + 65535)
+    if len(h) < 2 or h[0] != 0x1f or h[1] != 0x8b:
+        return "plain"
+    return "bgzf" if _bgzf_bsize(h, 0, len(h)) else "gzip"
+
+
+def _bgzf_members(path, buf):
+    """the member table of a BGZF file (``buf``: its bytes, a buffer), as the host walks a BAM's (csrc/host/mdk_io.c): [(file offset, stream
+    offset, stream length, ISIZE, CRC32)], empty members -- the EOF member is one -- left out.  A last member that is cut short, bytes that
+    are no BGZF header where one must stand and an ISIZE above 65536 raise MdkError; a missing EOF member does not (htslib warns and reads on)"""
+    out, o, end = [], 0, len(buf)
+    while o < end:
+        bs = _bgzf_bsize(buf, o, end)
+        if not bs:
+            if end - o < 18 or (buf[o] == 0x1f and buf[o + 1] == 0x8b and buf[o + 2] == 8 and buf[o + 3] == 4 and o + 12 + (buf[o + 10] | buf[o + 11] << 8) > end):
+                raise MdkError(f"{path}: the file is cut short inside the header of its last member (at byte {o})")
+            raise MdkError(f"{path}: no BGZF member at byte {o}: a gzip member without a BC subfield, or not gzip at all")
+        xlen = buf[o + 10] | buf[o + 11] << 8
+        if o + bs > end:
+            raise MdkError(f"{path}: the file is cut short inside its last member (at byte {o}: {bs} bytes by its header, {end - o} in the file)")
+        if bs < 12 + xlen + 8:
+            raise MdkError(f"{path}: the member at byte {o} is shorter than its own header and trailer")
+        crc, isz = struct.unpack_from("<II", buf, o + bs - 8)
+        if isz > 65536:
+            raise MdkError(f"{path}: the member at byte {o} inflates to {isz} bytes: a BGZF member holds at most 65536")
+        if isz:
+            out.append((o, o + 12 + xlen, bs - 12 - xlen - 8, isz, crc))
+        o += bs
+    return out
+
+
+def _gz_line_number(path, offset):
+    """the 1-based number of the line that holds byte ``offset`` of the decompressed text: the error path inflates on the host and counts newlines"""
+    import gzip
+    n, left = 1, offset
+    with gzip.open(path, "rb") as f:
+        while left > 0:
+            b = f.read(min(left, 1 << 24))
+            if not b:
+                break
+            n += b.count(b"\n"); left -= len(b)
+    return n
+
+
+def _device_last_newline(d, end):
+    """the index of the last newline in the device tensor ``d[:end]``, or -1 (searched backwards, 64 KiB at a time; one index crosses to the host)"""
+    while end > 0:
+        lo = max(0, end - 65536)
+        k = (d[lo:end] == 10).nonzero()
+        if k.numel():
+            return lo + int(k[-1])
+        end = lo
+    return -1
+
+
+def _parse_bgzf(L, text, path, fmt, columns, dev, block_bytes):
+    """``_parse_file`` for a BGZF file.  The host walks the headers into a member table; pieces of whole members -- at most ``block_bytes``
+    inflated bytes each, and at least one member -- go to the device through md_piece_submit (k_inflate, k_crc32), and their bytes are
+    parsed there.  bgzip cuts members every 65280 bytes, not at newlines: the bytes behind a piece's last newline stay on the device and
+    go in front of the next piece's.  No decompressed byte crosses to the host"""
+    import mmap
+    import re
+    import torch
+    out = []
+    if os.path.getsize(path) == 0:
+        return out
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as buf:
+        members = _bgzf_members(path, buf)
+        cfg = md_dev_cfg(); cfg.keepCpG = 1; cfg.minPhred = 5          # (a handle for the pieces: none of its settings touches the inflate)
+        handle, piece, stage, stage_cap = Device(cfg, device=dev.index or 0), C.c_void_p(), None, 0
+        try:
+            rc = L.md_piece_create(handle.h, C.byref(piece))
+            if rc:
+                raise _rc_error("md_piece_create", rc, L.md_dev_last_error().decode())
+            tail, at, k = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
+            while k < len(members):
+                k1, inflated = k, 0
+                while k1 < len(members) and (k1 == k or inflated + members[k1][3] <= block_bytes):
+                    inflated += members[k1][3]; k1 += 1
+                c0, c1 = members[k][1], members[k1 - 1][1] + members[k1 - 1][2]
+                if c1 - c0 + 64 > stage_cap:
+                    if stage:
+                        L.md_host_free(C.c_void_p(stage))
+                    stage_cap = c1 - c0 + (c1 - c0) // 8 + 64
+                    stage = L.md_host_alloc(stage_cap)
+                    if not stage:
+                        raise MdkError("no pinned memory for a piece of the file")
+                C.memmove(stage, buf[c0:c1], c1 - c0)
+                tab, o = (md_inf_member * (k1 - k))(), 0
+                for i in range(k, k1):
+                    _, so, sl, isz, crc = members[i]
+                    t = tab[i - k]
+                    t.in_off, t.in_len, t.out_len, t.out_off, t.crc32 = so - c0, sl, isz, o, crc
+                    o += isz
+                info = md_piece_info()
+                rc = L.md_piece_submit(piece, C.c_void_p(stage), c1 - c0, tab, k1 - k)
+                if not rc:
+                    rc = L.md_piece_wait(piece, C.byref(info))
+                if rc:
+                    detail = L.md_dev_last_error().decode()
+                    m = re.search(r"member (\d+) of the piece", detail)
+                    if m and int(m.group(1)) < k1 - k:
+                        detail = f"the member at byte {members[k + int(m.group(1))][0]} of the file: {detail}"
+                    raise _rc_error("reading", rc, f"{path}: {detail}")
+                keep = tail.numel()
+                d = torch.empty(keep + inflated, dtype=torch.uint8, device=dev)
+                d[:keep] = tail
+                torch.cuda.current_stream(dev).synchronize()         # the carried bytes are in place before the piece's are put behind them
+                rc = L.md_piece_copy(piece, 0, inflated, C.c_void_p(d.data_ptr() + keep))
+                if rc:
+                    raise _rc_error("md_piece_copy", rc, L.md_dev_last_error().decode())
+                end = keep + inflated
+                cut = end if k1 == len(members) else _device_last_newline(d, end) + 1
+                if cut == 0:
+                    raise MdkError(f"{path}: a line longer than block_bytes ({block_bytes}) at byte {at} of the decompressed text")
+                tail = d[cut:end].clone()
+                torch.cuda.current_stream(dev).synchronize()
+                out.append(_parse_text(L, text, d, cut, path, at, fmt, columns, dev, _gz_line_number))
+                at += cut; k = k1
+        finally:
+            if piece:
+                L.md_piece_destroy(piece)
+            if stage:
+                L.md_host_free(C.c_void_p(stage))
+            handle.close()
     return out
 
 
@@ -1166,25 +1391,32 @@ class Calls(_Columns):
             raise MdkError("the bedGraph header quotes the output prefix: give prefix=, or header=False")
         return f'track type="bedGraph" description="{prefix} {CONTEXT_FILES[context]}{" merged" if self.merged else ""} methylation {TEXT_WHAT[code]}"\n'.encode()
 
-    def render(self, fmt="bedGraph", context=0, prefix=None, header=True, block_rows=None):
+    def render(self, fmt="bedGraph", context=0, prefix=None, header=True, block_rows=None, compress=False):
         """The bytes of the file `extract -o prefix` writes for one context (0 CpG, 1 CHG, 2 CHH), as a uint8 tensor on the columns' device,
         made there (csrc/mdk_text.hip) from whatever the columns hold now -- the session's rows, or a filtered or re-ordered ``select``.
         ``fmt``: "bedGraph" (the default output), "fraction" (--fraction), "counts" (--counts) or "methylKit" (--methylKit); byte for byte the
         command's text, %f and %6.2f included.  "logit" raises MdkError with rc -23: --logit's value goes through log(), which is not
         correctly rounded on either side, so its bytes cannot be promised.  Rows of other contexts and rows without coverage give no line;
         a methylKit line of a --mergeContext row (strand 0) is an error, as the combination is for the command.  ``header=False`` leaves the
-        first line out.  CPU tensors raise MdkError: there is no CPU path."""
+        first line out.  ``compress=True`` gives the bytes of the .gz file instead: BGZF made on the device (``bgzf_compress``), the header
+        line and every block of ``block_rows`` rows in members of their own, one EOF member at the end; ``gzip.decompress`` of it is the
+        uncompressed result, whatever ``block_rows`` is.  CPU tensors raise MdkError: there is no CPU path."""
         code = self._format(fmt)
-        return self._render(code, int(context), self.header(fmt, int(context), prefix) if header else b"", block_rows)
+        return self._render(code, int(context), self.header(fmt, int(context), prefix) if header else b"", block_rows, compress)
 
-    def write(self, prefix, fmt="bedGraph", directory=None, block_rows=None):
+    def write(self, prefix, fmt="bedGraph", directory=None, block_rows=None, compress=False):
         """The command's file set under the command's names -- <prefix>_CpG.bedGraph, .meth.bedGraph (fraction), .counts.bedGraph,
         .methylKit --, one file per context in ``contexts_on``, header-only where there is no row; in ``directory`` if given.  The text is
         made on the device in blocks of ``block_rows`` rows (default 2^22), each copied to the host once and appended: the extra device and
-        pinned memory is one block's text, not the file's.  Returns the paths."""
+        pinned memory is one block's text, not the file's.  ``compress=True`` writes BGZF files under the same names with ``.gz`` appended:
+        every block is compressed on the device (csrc/mdk_deflate.hip) before its one copy to the host, so about a third of the bytes
+        cross; ``gzip``, ``zcat``, ``bgzip -d``, tabix and R read them, and ``gzip.decompress`` gives the uncompressed file byte for byte.
+        A header-only file is the header's member and the EOF member.  No tabix index is written, and there are no compression levels.
+        Returns the paths."""
         code = self._format(fmt)
-        return [self._write_file(os.path.join(directory, f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}") if directory is not None else f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}",
-                                 code, k, self.header(fmt, k, prefix), block_rows) for k in self.contexts_on]
+        gz = ".gz" if compress else ""
+        return [self._write_file(os.path.join(directory, f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}{gz}") if directory is not None else f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}{gz}",
+                                 code, k, self.header(fmt, k, prefix), block_rows, compress) for k in self.contexts_on]
 
     def merge_context(self, min_depth=1):
         """The rows the `mergeContext` command makes of these: a new Calls (``merged`` true, same ``contigs`` and ``contexts_on``, new tensors
@@ -1231,7 +1463,14 @@ class Calls(_Columns):
         to the device once; a line longer than a piece raises MdkError.  `track` lines are skipped wherever they stand.  The parser is
         stricter than the command (signs, blanks, doubled tabs, extra columns, numbers past INT32_MAX, merged files and lines longer than
         512 bytes are refused): MdkError with ``rc == -3`` names the refusal, the path and the line.  Only bedGraph files hold both counts:
-        --fraction, --counts and --methylKit files cannot be read, and neither can .gz files.  There is no CPU path."""
+        --fraction, --counts and --methylKit files cannot be read.  There is no CPU path.
+        BGZF files -- ``write(compress=True)``'s, bgzip's -- are read too, recognised by content (the gzip magic with FEXTRA and a BC
+        subfield), not by name: the host walks the 18-byte headers, pieces of whole members (``block_bytes`` counts inflated bytes) are
+        inflated and CRC32-checked on the device (csrc/mdk_inflate.hip) and parsed where they lie; a line may straddle members and
+        pieces, and no decompressed byte crosses to the host.  Refused, with MdkError naming the path: a gzip file that is not BGZF (one
+        member of any length is one wavefront's work: recompress it with bgzip), a member whose CRC32 or ISIZE does not check (with
+        the member's file offset), a last member that is cut short.  A missing EOF member is accepted, as htslib accepts it with a
+        warning.  A refused line's number is that of the decompressed text."""
         dev = _parse_device(device)
         if not isinstance(reference, Reference):
             raise MdkError("Calls.read needs a Reference: a bedGraph line's strand and context come from its bases")
@@ -1291,17 +1530,18 @@ class Reads(_Columns):
         view = md_reads_cols(*[C.c_void_p(t.data_ptr()) for t in cols])
         return self._text_iter(L, view, dev, TEXT_PERREAD, None, self._block_rows(block_rows))
 
-    def render(self, block_rows=None):
+    def render(self, block_rows=None, compress=False):
         """The bytes of the file `perRead -o` writes (no header: the command prints none), as a uint8 tensor on the columns' device, made
         there (k_rtext_len / k_rtext_fill, csrc/mdk_text.hip) from whatever the columns hold now: one line per row, covered or not.  A contig
         index outside ``contigs``, offsets that decrease or leave ``name_bytes``, and a name longer than 255 bytes raise MdkError; so do
-        CPU tensors: there is no CPU path."""
-        return self._render(TEXT_PERREAD, None, b"", block_rows)
+        CPU tensors: there is no CPU path.  ``compress=True``: the bytes of the BGZF file, as ``Calls.render``."""
+        return self._render(TEXT_PERREAD, None, b"", block_rows, compress)
 
-    def write(self, path, block_rows=None):
+    def write(self, path, block_rows=None, compress=False):
         """The file `perRead -o path` writes (``path`` is the file's name, not a prefix, as the command's -o is); blocks as ``Calls.write``.
-        No rows give an empty file.  Returns the path."""
-        return self._write_file(os.fspath(path), TEXT_PERREAD, None, b"", block_rows)
+        No rows give an empty file.  ``compress=True`` writes BGZF, compressed on the device as ``Calls.write`` does, to ``path`` as it is
+        given (nothing is appended); no rows give the EOF member alone.  Returns the path."""
+        return self._write_file(os.fspath(path), TEXT_PERREAD, None, b"", block_rows, compress)
 
     def select(self, index):
         """a copy with the rows ``index`` names -- a boolean mask, an int64 index tensor (any order, repeats allowed) or a slice --, same
@@ -1438,22 +1678,24 @@ class Cytosines(_Columns):
         c.contexts_on = tuple(k for k in range(3) if L.mdk_cytosines_contexts(out) >> k & 1)      # the contexts whose cytosines are rows
         return c
 
-    def render(self, block_rows=None):
+    def render(self, block_rows=None, compress=False):
         """The bytes of <prefix>.cytosine_report.txt (no header), as a uint8 tensor on the columns' device, made there from whatever the
-        columns hold now.  CPU tensors raise MdkError."""
-        return self._render(TEXT_CYTOSINE_REPORT, None, b"", block_rows)
+        columns hold now.  ``compress=True``: the bytes of the BGZF file, as ``Calls.render``.  CPU tensors raise MdkError."""
+        return self._render(TEXT_CYTOSINE_REPORT, None, b"", block_rows, compress)
 
-    def write(self, prefix, directory=None, block_rows=None):
-        """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  Returns the path."""
-        name = f"{prefix}.cytosine_report.txt"
-        return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows)
+    def write(self, prefix, directory=None, block_rows=None, compress=False):
+        """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  ``compress=True``
+        writes <prefix>.cytosine_report.txt.gz, BGZF compressed on the device as ``Calls.write`` does.  Returns the path."""
+        name = f"{prefix}.cytosine_report.txt" + (".gz" if compress else "")
+        return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows, compress)
 
     @classmethod
     def read(cls, path, contigs, device=0, contexts_on=None, block_bytes=None):
         """The rows of a <prefix>.cytosine_report.txt as a Cytosines on ``device``, parsed there (csrc/mdk_parse.hip), in the file's order.
         ``contigs`` is the list of names the lines' first column is looked up in (a session result's ``contigs``, a ``Reference``'s); no
         reference is needed: strand, context and trinucleotide are in the file.  ``contexts_on`` defaults to the contexts that have rows.
-        Pieces, refusals and errors as ``Calls.read``; .gz files cannot be read, and there is no CPU path.  Reports of several samples
+        Pieces, refusals and errors as ``Calls.read``, BGZF files (``write(compress=True)``'s, bgzip's) and what is refused of .gz files
+        included; there is no CPU path.  Reports of several samples
         read this way stack as a session's do: ``torch.stack([a.nmeth, b.nmeth])``."""
         dev = _parse_device(device)
         block_bytes = _parse_block_bytes(block_bytes)
@@ -1517,7 +1759,9 @@ class Intervals:
         session result's ``contigs``, a ``Reference``'s).  Fields are separated by tabs or blanks and only the first three are used;
         empty lines and lines that begin with ``#``, ``track`` or ``browser`` are skipped.  A contig that is not in ``contigs``, a
         field that is not a decimal number, ``end < start`` and a value above 2^31 - 1 raise MdkError with the path and the line
-        number.  Parsed on the host, line by line: a BED of islands or promoters has a few 10^5 lines.  .gz files cannot be read."""
+        number.  Parsed on the host, line by line: a BED of islands or promoters has a few 10^5 lines.  A file that begins with the gzip
+        magic -- plain gzip or BGZF -- is decompressed by the host's ``gzip`` module as it is read; one that does not inflate raises
+        MdkError with the path."""
         import torch
         path, contigs = os.fspath(bed_path), list(contigs)
         index = {}
@@ -1525,23 +1769,31 @@ class Intervals:
             index.setdefault(name, i)
         cols = ([], [], [])
         with open(path, "rb") as f:
-            for ln, raw in enumerate(f, 1):
-                fields = raw.decode("latin-1").split()
-                if not fields or fields[0].startswith("#") or fields[0] in ("track", "browser"):
-                    continue
-                if len(fields) < 3:
-                    raise MdkError(f"{path}:{ln}: a BED line has at least three fields")
-                if fields[0] not in index:
-                    raise MdkError(f"{path}:{ln}: the contig {fields[0]!r} is not among the contig names")
-                for v in fields[1:3]:
-                    if not (v.isascii() and v.isdigit()):
-                        raise MdkError(f"{path}:{ln}: {v!r} is not a decimal number")
-                s, e = int(fields[1]), int(fields[2])
-                if s > 2 ** 31 - 1 or e > 2 ** 31 - 1:
-                    raise MdkError(f"{path}:{ln}: a position above 2^31 - 1")
-                if e < s:
-                    raise MdkError(f"{path}:{ln}: end {e} < start {s}")
-                cols[0].append(index[fields[0]]); cols[1].append(s); cols[2].append(e)
+            data = f.read()
+        if data[:2] == b"\x1f\x8b":
+            import gzip
+            import zlib
+            try:
+                data = gzip.decompress(data)
+            except (OSError, EOFError, zlib.error) as e:
+                raise MdkError(f"{path}: not a readable gzip file: {e}") from None
+        for ln, raw in enumerate(data.split(b"\n")[:-1] if data.endswith(b"\n") else data.split(b"\n"), 1):
+            fields = raw.decode("latin-1").split()
+            if not fields or fields[0].startswith("#") or fields[0] in ("track", "browser"):
+                continue
+            if len(fields) < 3:
+                raise MdkError(f"{path}:{ln}: a BED line has at least three fields")
+            if fields[0] not in index:
+                raise MdkError(f"{path}:{ln}: the contig {fields[0]!r} is not among the contig names")
+            for v in fields[1:3]:
+                if not (v.isascii() and v.isdigit()):
+                    raise MdkError(f"{path}:{ln}: {v!r} is not a decimal number")
+            s, e = int(fields[1]), int(fields[2])
+            if s > 2 ** 31 - 1 or e > 2 ** 31 - 1:
+                raise MdkError(f"{path}:{ln}: a position above 2^31 - 1")
+            if e < s:
+                raise MdkError(f"{path}:{ln}: end {e} < start {s}")
+            cols[0].append(index[fields[0]]); cols[1].append(s); cols[2].append(e)
         return cls(contigs, *[torch.tensor(c, dtype=torch.int32) for c in cols])
 
     @classmethod

@@ -593,6 +593,14 @@ extern "C" int md_piece_read(md_piece *p, uint64_t off, uint64_t bytes, uint8_t 
     if(bytes) HIPCHK(hipMemcpy(dst, p->d_out.p + off, (size_t)bytes, hipMemcpyDeviceToHost));
     return 0;
 }
+// ... or to other DEVICE memory: text that is parsed where it lies (Calls.read of a .gz file joins a piece's bytes to the previous piece's last, cut line)
+extern "C" int md_piece_copy(md_piece *p, uint64_t off, uint64_t bytes, void *d_dst) {
+    if(!p || (bytes && !d_dst) || off + bytes > p->out_bytes) return fail(MDK_ERR_ARG, "md_piece_copy", hipSuccess);
+    HIPCHK(hipSetDevice(p->h->device));
+    HIPCHK(piece_sync(p));
+    if(bytes) HIPCHK(hipMemcpy(d_dst, p->d_out.p + off, (size_t)bytes, hipMemcpyDeviceToDevice));
+    return 0;
+}
 extern "C" int md_piece_read_records(md_piece *p, uint32_t first, uint32_t n, uint32_t *dst) {
     if(!p || !dst || (uint64_t)first + n > p->n_rec_cap) return fail(MDK_ERR_ARG, "md_piece_read_records", hipSuccess);
     HIPCHK(hipSetDevice(p->h->device));

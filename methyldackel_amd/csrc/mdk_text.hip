@@ -240,7 +240,7 @@ extern "C" void md_text_close(md_text *t) {
     if(!t) return;
     (void)hipSetDevice(t->device);
     if(t->st) { (void)hipStreamSynchronize(t->st); (void)hipStreamDestroy(t->st); }
-    text_parse_free(t); text_regions_free(t); text_unite_free(t); text_dmr_free(t);
+    text_parse_free(t); text_regions_free(t); text_unite_free(t); text_dmr_free(t); text_deflate_free(t);
     (void)hipFree(t->d_name_off); (void)hipFree(t->d_names); (void)hipFree(t->d_btot); (void)hipFree(t->d_boff); (void)hipFree(t->d_st);
     if(t->h_st) (void)hipHostFree(t->h_st);
     delete t;

@@ -89,6 +89,7 @@ struct KDmr {
     int32_t *o_contig, *o_start, *o_end, *o_nsites, *o_nsig; int8_t *o_dir; int64_t *o_a, *o_b, *o_c, *o_d; double *o_diff, *o_p; int64_t n_out;
 };
 struct DmrState;                                                          // mdk_dmr.hip: its buffers and what was measured
+struct DeflateState;                                                      // mdk_deflate.hip: the members' slots, lengths and token strips, and what was measured
 
 struct md_text {
     int device = 0; hipStream_t st = nullptr; int32_t n_contigs = 0;
@@ -105,6 +106,7 @@ struct md_text {
     uint32_t *d_rsites = nullptr; int64_t *d_rm = nullptr, *d_ru = nullptr; size_t cap_rblocks = 0;      // mdk_regions.hip: its prefix table, apart from d_btot / d_boff
     UniteState *unite = nullptr;                                      // mdk_unite.hip, made by the first md_text_unite_measure: tables of its own, too
     DmrState *dmr = nullptr;                                          // mdk_dmr.hip, made by the first md_text_dmr_measure: likewise
+    DeflateState *deflate = nullptr;                                  // mdk_deflate.hip, made by the first md_text_deflate_measure: likewise
 };
 
 // the block table for nb workgroups
@@ -117,6 +119,8 @@ MDK_HIDDEN void text_regions_free(md_text *t);
 MDK_HIDDEN void text_unite_free(md_text *t);
 // ... and mdk_dmr.hip
 MDK_HIDDEN void text_dmr_free(md_text *t);
+// ... and mdk_deflate.hip
+MDK_HIDDEN void text_deflate_free(md_text *t);
 
 // one workgroup of TEXT_SCAN_WG threads: the exclusive scan of the nb workgroup totals as int64 offsets, and their sum into the status block
 __device__ __forceinline__ void text_scan_blocks(const uint32_t *btot, int64_t *boff, TextStatus *st, uint32_t nb, int64_t *wtot) {
