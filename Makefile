@@ -23,7 +23,7 @@ $(B)/libmdk_extract.so: $(HOSTSRC) methyldackel_amd/csrc/host/mdk_io.h methyldac
 $(B)/MethylDackel: methyldackel_amd/csrc/host/main.c $(B)/libmdk_extract.so
 	$(CC) $(CFLAGS) -Iinclude -o $@ methyldackel_amd/csrc/host/main.c -L$(B) -lmdk_extract -lmdk_hip -Wl,-rpath,'$$ORIGIN' -lz -lm
 
-tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/diff_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
+tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/diff_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
 	@mkdir -p tools/_build
 	$(CC) -O2 -g -Wall -shared -fPIC -Iinclude -o $@ tools/piece_standin.c -lz
@@ -51,9 +51,12 @@ tools/_build/parse_emu: tools/parse_emu.cpp methyldackel_amd/csrc/mdk_parse_core
 tools/_build/region_emu: tools/region_emu.cpp methyldackel_amd/csrc/mdk_region_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/region_emu.cpp -Imethyldackel_amd/csrc
-tools/_build/deflate_emu: tools/deflate_emu.cpp methyldackel_amd/csrc/mdk_deflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h
+tools/_build/deflate_emu: tools/deflate_emu.cpp tools/deflate_walk.h methyldackel_amd/csrc/mdk_deflate_core.h methyldackel_amd/csrc/mdk_crc32_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/deflate_emu.cpp -Imethyldackel_amd/csrc
+tools/_build/bigwig_emu: tools/bigwig_emu.cpp tools/deflate_walk.h methyldackel_amd/csrc/mdk_bigwig_core.h methyldackel_amd/csrc/mdk_deflate_core.h
+	@mkdir -p tools/_build
+	g++ -O2 -Wall -ffp-contract=off -o $@ tools/bigwig_emu.cpp -Imethyldackel_amd/csrc
 tools/_build/unite_emu: tools/unite_emu.cpp methyldackel_amd/csrc/mdk_unite_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/unite_emu.cpp -Imethyldackel_amd/csrc
