@@ -22,6 +22,7 @@ REPO = ROOT.parent
 BUILD = Path(os.environ["MDK_BUILD_DIR"]) if os.environ.get("MDK_BUILD_DIR") else ROOT / "_build"      # MDK_BUILD_DIR: experiment builds (tools/kbench.py)
 LIB_HIP = BUILD / "libmdk_hip.so"
 LIB_EXTRACT = BUILD / "libmdk_extract.so"
+LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
 CLI = BUILD / "MethylDackel"
 
 CHUNK_NOREF, CHUNK_FOREIGN, CHUNK_BED = 1, 2, 4
@@ -967,14 +968,20 @@ class _Columns:
                 raise _rc_error("md_text_fill", rc, L.md_dev_last_error().decode())
             yield out
 
-    def _compressed(self, blocks, head, dev):
-        """the header line and every block of text as BGZF members on the device (a member never spans two blocks; the header's are its own)"""
+    def _compressed(self, blocks, head, dev, feed=None):
+        """the header line and every block of text as BGZF members on the device (a member never spans two blocks; the header's are its own).
+        ``feed``: every piece of text is shown to it before it is deflated (the tabix indexer: the text is on the device just then)"""
         import torch
         L = _text_lib()
         if head:
-            yield _deflate(L, self._text, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev), False)
+            h = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev)
+            if feed:
+                feed(h)
+            yield _deflate(L, self._text, h, False)
         for b in blocks:
             if b.numel():
+                if feed:
+                    feed(b)
                 yield _deflate(L, self._text, b, False)
 
     def _render(self, fmt, context, head, block_rows, compress=False):
@@ -989,27 +996,45 @@ class _Columns:
             parts.insert(0, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
         return torch.cat(parts) if len(parts) > 1 else parts[0] if parts else torch.empty(0, dtype=torch.uint8, device=dev)
 
-    def _write_file(self, path, fmt, context, head, block_rows, compress=False):
+    def _write_file(self, path, fmt, context, head, block_rows, compress=False, index=None):
         """the header, then every block of text: one device-to-host copy into a pinned buffer each, appended to the file.  ``compress``: the
-        header and every block are BGZF members by then (k_deflate), and one EOF member ends the file"""
+        header and every block are BGZF members by then (k_deflate), and one EOF member ends the file.  ``index``: a tabix configuration;
+        every piece of text is fed to the indexer on its way to the deflate, the member table is walked from the compressed bytes as
+        they pass, and ``path + ".tbi"`` is written behind the file.  A refused row lets the data file finish, then raises"""
         import torch
-        pin, blocks = None, self._text_blocks(fmt, context, block_rows)
-        if compress:
-            blocks, head, tail = self._compressed(blocks, head, getattr(self, self.COLUMNS[0][0]).device), b"", BGZF_EOF
-        else:
-            tail = b""
-        with open(path, "wb") as f:
-            f.write(head)
-            for b in blocks:
-                n = b.numel()
-                if not n:
-                    continue
-                if pin is None or pin.numel() < n:
-                    pin = torch.empty(n + n // 8, dtype=torch.uint8, pin_memory=True)
-                pin[:n].copy_(b, non_blocking=True)
-                torch.cuda.current_stream(b.device).synchronize()
-                f.write(memoryview(pin.numpy())[:n])
-            f.write(tail)
+        if index is not None and not compress:
+            raise MdkError("index=True needs compress=True: a tabix index is the index of a BGZF file")
+        pin, blocks, ix = None, self._text_blocks(fmt, context, block_rows), None
+        try:
+            if compress:
+                dev = getattr(self, self.COLUMNS[0][0]).device
+                if index is not None:
+                    ix = _TabixIndexer(path, index, dev)
+                blocks, head, tail = self._compressed(blocks, head, dev, ix.feed if ix else None), b"", BGZF_EOF
+            else:
+                tail = b""
+            with open(path, "wb") as f:
+                f.write(head)
+                at = len(head)
+                for b in blocks:
+                    n = b.numel()
+                    if not n:
+                        continue
+                    if pin is None or pin.numel() < n:
+                        pin = torch.empty(n + n // 8, dtype=torch.uint8, pin_memory=True)
+                    pin[:n].copy_(b, non_blocking=True)
+                    torch.cuda.current_stream(b.device).synchronize()
+                    view = memoryview(pin.numpy())[:n]
+                    if ix:
+                        ix.members_of(view, at)
+                    f.write(view)
+                    at += n
+                f.write(tail)
+            if ix:
+                ix.finish()
+        finally:
+            if ix:
+                ix.close()
         return path
 
 
@@ -1273,72 +1298,382 @@ def _parse_bgzf(L, text, path, fmt, columns, dev, block_bytes):
     inflated bytes each, and at least one member -- go to the device through md_piece_submit (k_inflate, k_crc32), and their bytes are
     parsed there.  bgzip cuts members every 65280 bytes, not at newlines: the bytes behind a piece's last newline stay on the device and
     go in front of the next piece's.  No decompressed byte crosses to the host"""
+    import contextlib
     import mmap
-    import re
-    import torch
     out = []
     if os.path.getsize(path) == 0:
         return out
     with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as buf:
-        members = _bgzf_members(path, buf)
-        cfg = md_dev_cfg(); cfg.keepCpG = 1; cfg.minPhred = 5          # (a handle for the pieces: none of its settings touches the inflate)
-        handle, piece, stage, stage_cap = Device(cfg, device=dev.index or 0), C.c_void_p(), None, 0
-        try:
-            rc = L.md_piece_create(handle.h, C.byref(piece))
+        with contextlib.closing(_bgzf_pieces(L, path, buf, _bgzf_members(path, buf), dev, block_bytes)) as pieces:
+            for d, cut, at in pieces:
+                out.append(_parse_text(L, text, d, cut, path, at, fmt, columns, dev, _gz_line_number))
+    return out
+
+
+def _bgzf_pieces(L, path, buf, members, dev, block_bytes, drop=0, limit=None):
+    """the text of ``members`` (entries of ``_bgzf_members`` that follow each other in ``buf``, the file's bytes) as pieces of whole lines: a
+    generator of (device tensor, the bytes at its start that are the piece, their offset in the text).  ``_parse_bgzf``'s pieces; a region
+    read gives the members of one chunk, with ``drop`` bytes of the first member left out in front (the text begins there) and the text
+    ended after ``limit`` bytes"""
+    import re
+    import torch
+    cfg = md_dev_cfg(); cfg.keepCpG = 1; cfg.minPhred = 5          # (a handle for the pieces: none of its settings touches the inflate)
+    handle, piece, stage, stage_cap = Device(cfg, device=dev.index or 0), C.c_void_p(), None, 0
+    try:
+        rc = L.md_piece_create(handle.h, C.byref(piece))
+        if rc:
+            raise _rc_error("md_piece_create", rc, L.md_dev_last_error().decode())
+        tail, at, k = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
+        while k < len(members) and (limit is None or at + tail.numel() < limit):
+            k1, inflated = k, 0
+            while k1 < len(members) and (k1 == k or inflated + members[k1][3] <= block_bytes):
+                inflated += members[k1][3]; k1 += 1
+            c0, c1 = members[k][1], members[k1 - 1][1] + members[k1 - 1][2]
+            if c1 - c0 + 64 > stage_cap:
+                if stage:
+                    L.md_host_free(C.c_void_p(stage))
+                stage_cap = c1 - c0 + (c1 - c0) // 8 + 64
+                stage = L.md_host_alloc(stage_cap)
+                if not stage:
+                    raise MdkError("no pinned memory for a piece of the file")
+            C.memmove(stage, buf[c0:c1], c1 - c0)
+            tab, o = (md_inf_member * (k1 - k))(), 0
+            for i in range(k, k1):
+                _, so, sl, isz, crc = members[i]
+                t = tab[i - k]
+                t.in_off, t.in_len, t.out_len, t.out_off, t.crc32 = so - c0, sl, isz, o, crc
+                o += isz
+            info = md_piece_info()
+            rc = L.md_piece_submit(piece, C.c_void_p(stage), c1 - c0, tab, k1 - k)
+            if not rc:
+                rc = L.md_piece_wait(piece, C.byref(info))
             if rc:
-                raise _rc_error("md_piece_create", rc, L.md_dev_last_error().decode())
-            tail, at, k = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
-            while k < len(members):
-                k1, inflated = k, 0
-                while k1 < len(members) and (k1 == k or inflated + members[k1][3] <= block_bytes):
-                    inflated += members[k1][3]; k1 += 1
-                c0, c1 = members[k][1], members[k1 - 1][1] + members[k1 - 1][2]
-                if c1 - c0 + 64 > stage_cap:
-                    if stage:
-                        L.md_host_free(C.c_void_p(stage))
-                    stage_cap = c1 - c0 + (c1 - c0) // 8 + 64
-                    stage = L.md_host_alloc(stage_cap)
-                    if not stage:
-                        raise MdkError("no pinned memory for a piece of the file")
-                C.memmove(stage, buf[c0:c1], c1 - c0)
-                tab, o = (md_inf_member * (k1 - k))(), 0
-                for i in range(k, k1):
-                    _, so, sl, isz, crc = members[i]
-                    t = tab[i - k]
-                    t.in_off, t.in_len, t.out_len, t.out_off, t.crc32 = so - c0, sl, isz, o, crc
-                    o += isz
-                info = md_piece_info()
-                rc = L.md_piece_submit(piece, C.c_void_p(stage), c1 - c0, tab, k1 - k)
-                if not rc:
-                    rc = L.md_piece_wait(piece, C.byref(info))
-                if rc:
-                    detail = L.md_dev_last_error().decode()
-                    m = re.search(r"member (\d+) of the piece", detail)
-                    if m and int(m.group(1)) < k1 - k:
-                        detail = f"the member at byte {members[k + int(m.group(1))][0]} of the file: {detail}"
-                    raise _rc_error("reading", rc, f"{path}: {detail}")
-                keep = tail.numel()
-                d = torch.empty(keep + inflated, dtype=torch.uint8, device=dev)
-                d[:keep] = tail
-                torch.cuda.current_stream(dev).synchronize()         # the carried bytes are in place before the piece's are put behind them
-                rc = L.md_piece_copy(piece, 0, inflated, C.c_void_p(d.data_ptr() + keep))
+                detail = L.md_dev_last_error().decode()
+                m = re.search(r"member (\d+) of the piece", detail)
+                if m and int(m.group(1)) < k1 - k:
+                    detail = f"the member at byte {members[k + int(m.group(1))][0]} of the file: {detail}"
+                raise _rc_error("reading", rc, f"{path}: {detail}")
+            keep, skip = tail.numel(), drop if k == 0 else 0
+            take = max(0, inflated - skip)
+            if limit is not None:
+                take = min(take, limit - at - keep)
+            d = torch.empty(keep + take, dtype=torch.uint8, device=dev)
+            d[:keep] = tail
+            torch.cuda.current_stream(dev).synchronize()         # the carried bytes are in place before the piece's are put behind them
+            if take:
+                rc = L.md_piece_copy(piece, skip, take, C.c_void_p(d.data_ptr() + keep))
                 if rc:
                     raise _rc_error("md_piece_copy", rc, L.md_dev_last_error().decode())
-                end = keep + inflated
-                cut = end if k1 == len(members) else _device_last_newline(d, end) + 1
-                if cut == 0:
-                    raise MdkError(f"{path}: a line longer than block_bytes ({block_bytes}) at byte {at} of the decompressed text")
-                tail = d[cut:end].clone()
-                torch.cuda.current_stream(dev).synchronize()
-                out.append(_parse_text(L, text, d, cut, path, at, fmt, columns, dev, _gz_line_number))
-                at += cut; k = k1
+            end = keep + take
+            cut = end if k1 == len(members) or (limit is not None and at + end >= limit) else _device_last_newline(d, end) + 1
+            if cut == 0:
+                raise MdkError(f"{path}: a line longer than block_bytes ({block_bytes}) at byte {at} of the decompressed text")
+            tail = d[cut:end].clone()
+            torch.cuda.current_stream(dev).synchronize()
+            yield d, cut, at
+            at += cut; k = k1
+    finally:
+        if piece:
+            L.md_piece_destroy(piece)
+        if stage:
+            L.md_host_free(C.c_void_p(stage))
+        handle.close()
+
+
+# ---- tabix indexes (include/mdk_index.h, csrc/mdk_tabix.hip -> libmdk_index.so; the rule is csrc/mdk_tabix_core.h) ----
+TABIX_UCSC = 0x10000
+TABIX_PRESETS = {"bed": (TABIX_UCSC, 1, 2, 3, ord("#")), "methylKit": (0, 2, 3, 3, ord("#")), "cytosine_report": (0, 1, 2, 2, ord("#"))}
+_index = None
+
+
+class md_index_conf(C.Structure):
+    _fields_ = [("format", C.c_int32), ("col_seq", C.c_int32), ("col_beg", C.c_int32), ("col_end", C.c_int32), ("meta", C.c_int32), ("skip", C.c_int32)]
+
+
+class md_index_member(C.Structure):
+    _fields_ = [("c_off", C.c_uint64), ("u_off", C.c_uint64), ("isize", C.c_uint32), ("pad", C.c_uint32)]
+
+
+def lib_index():
+    """libmdk_index.so, loaded at the first index call: its code object's load is paid there and by no command"""
+    global _index
+    if _index is None:
+        if not LIB_INDEX.exists():
+            raise MdkError(f"{LIB_INDEX} is missing: the index library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+        L = C.CDLL(str(LIB_INDEX))
+        L.md_index_last_error.restype = C.c_char_p
+        L.md_index_open.argtypes = [C.c_int, C.POINTER(md_index_conf), C.POINTER(C.c_void_p)]
+        L.md_index_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.md_index_refusal.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.md_index_finish.argtypes = [C.c_void_p, C.POINTER(md_index_member), C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]
+        L.md_index_payload.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.md_index_count.argtypes = [C.c_void_p, C.c_int]; L.md_index_count.restype = C.c_int64
+        L.md_index_close.argtypes = [C.c_void_p]; L.md_index_close.restype = None
+        _index = L
+    return _index
+
+
+def _tabix_conf(preset, skip):
+    if preset not in TABIX_PRESETS:
+        raise MdkError(f"unknown preset {preset!r}: one of {', '.join(TABIX_PRESETS)}")
+    skip = int(skip)
+    if not 0 <= skip <= 2 ** 31 - 1:
+        raise MdkError("skip must be between 0 and 2^31 - 1")
+    return TABIX_PRESETS[preset] + (skip,)
+
+
+class _TabixIndexer:
+    """one md_index: the text of the data file ``path`` is fed piece by piece (device tensors of whole lines), the members that hold bytes
+    are noted as the compressed bytes pass, and ``finish`` writes ``path + ".tbi"``: the payload through ``bgzf_compress``"""
+
+    def __init__(self, path, conf, dev):
+        self.L, self.h, self.path, self.dev = lib_index(), C.c_void_p(), path, dev
+        self.members, self.u, self.c_end, self.error, self.counts = [], 0, 0, None, None
+        if os.path.exists(path + ".tbi"):
+            os.remove(path + ".tbi")                                 # (an index of the file that stood here before is the index of another file)
+        rc = self.L.md_index_open(dev.index or 0, C.byref(md_index_conf(*conf)), C.byref(self.h))
+        if rc:
+            self.h = None
+            raise _rc_error("md_index_open", rc, self.L.md_index_last_error().decode())
+
+    def feed(self, t):
+        import torch
+        if self.error is not None or not t.numel():
+            return
+        torch.cuda.current_stream(t.device).synchronize()            # the text is complete
+        rc = self.L.md_index_feed(self.h, C.c_void_p(t.data_ptr()), t.numel())
+        if rc == 1:
+            self.error = _rc_error("indexing", -3, f"{self.path}, {self.L.md_index_last_error().decode()}: no tabix index is written")
+        elif rc:
+            raise _rc_error("md_index_feed", rc, self.L.md_index_last_error().decode())
+
+    def members_of(self, buf, at):
+        """the members in ``buf``, whole BGZF members that stand at byte ``at`` of the file"""
+        o, end = 0, len(buf)
+        while o < end:
+            if o + 18 <= end and buf[o + 12:o + 16] == b"BC\x02\x00" and buf[o:o + 4] == b"\x1f\x8b\x08\x04":      # k_deflate's header: BSIZE stands at 16
+                bs = (buf[o + 16] | buf[o + 17] << 8) + 1
+            else:
+                bs = _bgzf_bsize(buf, o, end)
+            if not bs or o + bs > end:
+                raise MdkError(f"{self.path}: no whole BGZF member at byte {at + o}")
+            self.member(at + o, bs, struct.unpack_from("<I", buf, o + bs - 4)[0])
+            o += bs
+
+    def member(self, c, bs, isize):
+        if isize:
+            self.members.append((c, self.u, isize))
+            self.u += isize; self.c_end = c + bs
+
+    def finish(self):
+        import torch
+        if self.error is not None:
+            raise self.error
+        tab, size = (md_index_member * max(1, len(self.members)))(), C.c_int64()
+        for t, (c, u, n) in zip(tab, self.members):
+            t.c_off, t.u_off, t.isize = c, u, n
+        rc = self.L.md_index_finish(self.h, tab, len(self.members), self.c_end, C.byref(size))
+        if rc:
+            raise _rc_error("md_index_finish", rc, f"{self.path}: {self.L.md_index_last_error().decode()}")
+        payload = bytearray(size.value)
+        rc = self.L.md_index_payload(self.h, (C.c_char * size.value).from_buffer(payload), size.value)
+        if rc:
+            raise _rc_error("md_index_payload", rc, self.L.md_index_last_error().decode())
+        self.counts = {k: int(self.L.md_index_count(self.h, i)) for i, k in enumerate(("lines", "entries", "records", "names", "pieces"))}
+        data = bgzf_compress(torch.frombuffer(payload, dtype=torch.uint8).to(self.dev))
+        with open(self.path + ".tbi", "wb") as f:
+            f.write(bytes(data.cpu().numpy()))
+        return self.path + ".tbi"
+
+    def close(self):
+        if self.h:
+            self.L.md_index_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tabix_index(path, preset="bed", skip=None, device=0, block_bytes=None):
+    """``path + ".tbi"``: the tabix index of any BGZF table -- ``write(compress=True)``'s, bgzip's, last week's, the command line's output
+    compressed afterwards --, what `tabix -p bed` would be run for.  The file's members are inflated and CRC32-checked on the device in
+    pieces (as ``Calls.read`` reads them), every line is parsed there (csrc/mdk_tabix.hip), and the few records that are left become the
+    index on the host; it is written as BGZF made on the device.  ``preset``: "bed" (columns 1, 2, 3, 0-based half-open: the bedGraph,
+    --fraction and --counts files), "methylKit" (columns 2 and 3) or "cytosine_report" (columns 1 and 2).  ``skip``: the number of lines
+    at the file's start that are no rows; by default 1 for a methylKit file, 0 for a report and, for "bed", 1 if the text begins with
+    `track`.  Lines that begin with '#' are passed over.  The bytes of the index depend on the data file alone (csrc/mdk_tabix_core.h
+    fixes what the specification leaves open).  Refused, with MdkError naming the path and the line, and no .tbi left behind: rows that
+    are not sorted by (contig, begin), a contig that appears in two places, an interval past 2^29 (a .tbi ends at 512 Mb; CSI is not
+    written), malformed coordinates, lines longer than 512 bytes, empty lines; and, as ``Calls.read`` refuses it, a gzip file that is
+    not BGZF.  perRead files, ``Regions`` / ``Diff`` / ``Dmrs`` files and the `MethylDackel` command line are out of scope.  Returns
+    the index's path.  There is no CPU path."""
+    import contextlib
+    import mmap
+    import zlib
+    path = os.fsdecode(path)
+    dev = _parse_device(device)
+    block_bytes = _parse_block_bytes(block_bytes)
+    kind = _gz_kind(path)
+    if kind != "bgzf":
+        raise MdkError(f"{path}: " + ("a gzip file that is not BGZF (no BC subfield in its header): recompress it with bgzip" if kind == "gzip" else
+                                      "not a BGZF file: a tabix index is the index of a BGZF file (write(compress=True), bgzip)"))
+    L = _text_lib()
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as buf:
+        members = _bgzf_members(path, buf)
+        if skip is None:
+            skip = {"methylKit": 1, "cytosine_report": 0}.get(preset)
+            if skip is None:
+                first = b""                                          # the text's first five bytes: members may be as short as one byte
+                for _, so, sl, _, _ in members:
+                    if len(first) >= 5:
+                        break
+                    first += zlib.decompress(buf[so:so + sl], -15)
+                skip = 1 if first[:5] == b"track" else 0
+        ix = _TabixIndexer(path, _tabix_conf(preset, skip), dev)
+        try:
+            for o, so, sl, isz, _ in members:
+                ix.member(o, so + sl + 8 - o, isz)
+            with contextlib.closing(_bgzf_pieces(L, path, buf, members, dev, block_bytes)) as pieces:
+                for d, cut, _ in pieces:
+                    ix.feed(d[:cut])
+            return ix.finish()
         finally:
-            if piece:
-                L.md_piece_destroy(piece)
-            if stage:
-                L.md_host_free(C.c_void_p(stage))
-            handle.close()
+            ix.close()
+
+
+def _tabix_chunks(path, name, beg, end):
+    """the chunks of the .tbi ``path`` that may hold a line overlapping name:[beg, end), as [[begin, end]] virtual offsets, ascending,
+    neighbours joined: those of the region's bins (reg2bins of the specification) that end above the linear index's offset for the
+    region's first window.  The index is read on the host (it is small, and the gzip module does); only the asked name's bins are
+    looked at, with numpy where every bin has one chunk, as the bins of ``write``'s and ``tabix_index``'s files have"""
+    import gzip
+    import zlib
+    import numpy as np
+    try:
+        with open(path, "rb") as f:
+            p = gzip.decompress(f.read())
+    except FileNotFoundError:
+        raise MdkError(f"{path}: no tabix index: a region is read through the index (write(..., compress=True, index=True), tabix_index)") from None
+    except (OSError, EOFError, zlib.error) as e:
+        raise MdkError(f"{path}: not a tabix index: {e}") from None
+    try:
+        if p[:4] != b"TBI\x01":
+            raise ValueError("no TBI magic")
+        n_ref, l_nm = struct.unpack_from("<i", p, 4)[0], struct.unpack_from("<i", p, 32)[0]
+        names, o = [os.fsdecode(x) for x in p[36:36 + l_nm].split(b"\0")[:-1]], 36 + l_nm
+        if len(names) != n_ref:
+            raise ValueError("the names do not match n_ref")
+        if name not in names:
+            return []
+        tid, wanted, found, head = names.index(name), _tabix_bins(beg, end), [], struct.Struct("<Ii").unpack_from
+        for t in range(tid + 1):
+            n_bin, = struct.unpack_from("<i", p, o); o += 4
+            k = 0
+            if n_bin > 1 and o + 24 * (n_bin - 1) <= len(p):
+                words = np.frombuffer(p, dtype="<u4", count=6 * (n_bin - 1), offset=o)
+                if bool((words[1::6] == 1).all()):               # one chunk in each of the first n_bin - 1 bins: they stand 24 bytes apart
+                    k = n_bin - 1
+                    if t == tid:
+                        for i in np.nonzero(np.isin(words[0::6], np.asarray(wanted, dtype=np.uint32)))[0].tolist():
+                            found.append(struct.unpack_from("<QQ", p, o + 24 * i + 8))
+                    o += 24 * k
+            wanted_set = set(wanted) if t == tid and k < n_bin else ()
+            for _ in range(k, n_bin):
+                b, n_chunk = head(p, o); o += 8
+                if n_chunk < 0:
+                    raise ValueError("a negative chunk count")
+                if b in wanted_set:
+                    found += [struct.unpack_from("<QQ", p, o + 16 * c) for c in range(n_chunk)]
+                o += 16 * n_chunk
+            n_intv, = struct.unpack_from("<i", p, o); o += 4
+            if t == tid:
+                if beg >> 14 >= n_intv:
+                    return []
+                low, = struct.unpack_from("<Q", p, o + 8 * (beg >> 14))
+            o += 8 * n_intv
+            if o > len(p):
+                raise ValueError("cut short")
+    except (struct.error, ValueError) as e:
+        raise MdkError(f"{path}: not a tabix index: {e}") from None
+    chunks = []
+    for vb, ve in sorted(ch for ch in found if ch[1] > low):
+        if chunks and vb <= chunks[-1][1]:
+            chunks[-1][1] = max(chunks[-1][1], ve)
+        else:
+            chunks.append([vb, ve])
+    return chunks
+
+
+def _tabix_bins(beg, end):
+    """the bins that may hold an interval overlapping [beg, end): reg2bins of the specification"""
+    end -= 1
+    out = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        out += range(first + (beg >> shift), first + (end >> shift) + 1)
     return out
+
+
+def _region_check(region):
+    try:
+        name, beg, end = region
+        beg, end = int(beg), int(end)
+    except (TypeError, ValueError):
+        raise MdkError("region must be (name, beg, end): a contig name and a 0-based half-open interval") from None
+    if not 0 <= beg < end:
+        raise MdkError("region must be (name, beg, end) with 0 <= beg < end")
+    return str(name), beg, min(end, 1 << 29)
+
+
+def _parse_region(L, text, path, fmt, columns, dev, block_bytes, region, stats):
+    """``_parse_file`` for the lines a tabix index says may overlap ``region``: the chunks of the region's bins that end above the linear
+    index's offset for the region's first window, neighbours joined; of the file only the members those chunks span are inflated, and only
+    the text between a chunk's begin and end is parsed; the member headers of those chunks alone are walked.  ``stats`` takes the count
+    of members inflated"""
+    import contextlib
+    import mmap
+    if isinstance(path, (list, tuple)):
+        raise MdkError("a region is read from one file: every file has an index of its own")
+    path = os.fsdecode(path)
+    name, beg, end = region
+    kind = _gz_kind(path)
+    if kind != "bgzf":
+        raise MdkError(f"{path}: a region is read through a tabix index, which only a BGZF file has (write(..., compress=True, index=True))")
+    chunks = _tabix_chunks(path + ".tbi", name, beg, end)
+    out, stats["members_inflated"] = [], 0
+    if not chunks:
+        return out
+    misfit = MdkError(f"{path}.tbi: the index does not fit the file: no member where a chunk begins or ends. Index it again (tabix_index)")
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as buf:
+        for vb, ve in chunks:
+            c0, c1 = vb >> 16, ve >> 16
+            if ve & 0xffff:                                           # the chunk ends inside the member at c1: that member too
+                bs = _bgzf_bsize(buf, c1, len(buf)) if c1 < len(buf) else 0
+                if not bs:
+                    raise misfit
+                c1 += bs
+            if not c0 < c1 <= len(buf) or not _bgzf_bsize(buf, c0, len(buf)):
+                raise misfit
+            members = [(c0 + o, c0 + so, sl, isz, crc) for o, so, sl, isz, crc in _bgzf_members(path, buf[c0:c1])]      # the chunk's members alone are walked
+            if not members or members[0][0] != c0 or vb & 0xffff >= members[0][3] or (ve & 0xffff and (members[-1][0] != ve >> 16 or ve & 0xffff > members[-1][3])):
+                raise misfit
+            limit = sum(m[3] for m in members) - (vb & 0xffff) - (members[-1][3] - (ve & 0xffff) if ve & 0xffff else 0)
+            stats["members_inflated"] += len(members)
+            with contextlib.closing(_bgzf_pieces(L, path, buf, members, dev, block_bytes, drop=vb & 0xffff, limit=limit)) as pieces:
+                for d, cut, at in pieces:
+                    out.append(_parse_text(L, text, d, cut, path, at, fmt, columns, dev, lambda p, o, vb=vb: _region_line_number(p, vb, o)))
+    return out
+
+
+def _region_line_number(path, vb, offset):
+    """the 1-based line that holds the byte ``offset`` bytes behind virtual offset ``vb``: the error path walks the file on the host"""
+    import gzip
+    with open(path, "rb") as f:
+        raw = f.read()
+    before = gzip.decompress(raw[:vb >> 16]) if vb >> 16 else b""
+    return _gz_line_number(path, len(before) + (vb & 0xffff) + offset)
 
 
 def _parse_cat(pieces, columns, dev):
@@ -1404,19 +1739,30 @@ class Calls(_Columns):
         code = self._format(fmt)
         return self._render(code, int(context), self.header(fmt, int(context), prefix) if header else b"", block_rows, compress)
 
-    def write(self, prefix, fmt="bedGraph", directory=None, block_rows=None, compress=False):
+    def write(self, prefix, fmt="bedGraph", directory=None, block_rows=None, compress=False, index=False):
         """The command's file set under the command's names -- <prefix>_CpG.bedGraph, .meth.bedGraph (fraction), .counts.bedGraph,
         .methylKit --, one file per context in ``contexts_on``, header-only where there is no row; in ``directory`` if given.  The text is
         made on the device in blocks of ``block_rows`` rows (default 2^22), each copied to the host once and appended: the extra device and
         pinned memory is one block's text, not the file's.  ``compress=True`` writes BGZF files under the same names with ``.gz`` appended:
         every block is compressed on the device (csrc/mdk_deflate.hip) before its one copy to the host, so about a third of the bytes
         cross; ``gzip``, ``zcat``, ``bgzip -d``, tabix and R read them, and ``gzip.decompress`` gives the uncompressed file byte for byte.
-        A header-only file is the header's member and the EOF member.  No tabix index is written, and there are no compression levels.
+        A header-only file is the header's member and the EOF member.  There are no compression levels.
+        ``index=True`` (with ``compress=True``; without it MdkError) writes <file>.gz.tbi next to every .gz: the tabix index methylKit's
+        tabix-backed objects, IGV and `tabix file.gz chr2:1-2000000` open first, and the one ``read(region=)`` reads through; for a
+        header-only file too (no names in it).  The text is indexed on the device (csrc/mdk_tabix.hip) on its way to the deflate --
+        nothing is inflated again --, the member table is walked from the compressed bytes that cross to the host anyway, and the index
+        is that of ``tabix_index`` for the same file, byte for byte (the bedGraph kinds as `-p bed` with the header line skipped,
+        methylKit by its chr and base columns).  Rows the rule refuses -- out of order after a ``select``, a contig in two places, a row
+        past 2^29: a .tbi ends at 512 Mb, and CSI is not written -- raise MdkError (rc -3) with the file and the line after the data
+        file is complete, and no .tbi is left behind.
         Returns the paths."""
         code = self._format(fmt)
         gz = ".gz" if compress else ""
+        if index and not compress:
+            raise MdkError("index=True needs compress=True: a tabix index is the index of a BGZF file")
+        conf = _tabix_conf("methylKit" if fmt == "methylKit" else "bed", 1) if index else None
         return [self._write_file(os.path.join(directory, f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}{gz}") if directory is not None else f"{prefix}_{CONTEXT_FILES[k]}{TEXT_SUFFIX[code]}{gz}",
-                                 code, k, self.header(fmt, k, prefix), block_rows, compress) for k in self.contexts_on]
+                                 code, k, self.header(fmt, k, prefix), block_rows, compress, conf) for k in self.contexts_on]
 
     def merge_context(self, min_depth=1):
         """The rows the `mergeContext` command makes of these: a new Calls (``merged`` true, same ``contigs`` and ``contexts_on``, new tensors
@@ -1451,7 +1797,7 @@ class Calls(_Columns):
         return self._regions([getattr(self, name) for name, _ in CALL_COLUMNS], intervals, contexts, strand, min_depth)
 
     @classmethod
-    def read(cls, paths, reference, device=0, contexts_on=None, block_bytes=None):
+    def read(cls, paths, reference, device=0, contexts_on=None, block_bytes=None, region=None):
         """The rows of per-cytosine bedGraph files -- what ``write`` made, last week's run, the command-line tool's output -- as a Calls on
         ``device``, parsed there (csrc/mdk_parse.hip): no line passes through Python.  ``paths`` is one path or a list; the rows come in the
         order of the paths, then of the lines (``sorted()`` makes the three per-context files of one run the ascending table
@@ -1470,12 +1816,30 @@ class Calls(_Columns):
         pieces, and no decompressed byte crosses to the host.  Refused, with MdkError naming the path: a gzip file that is not BGZF (one
         member of any length is one wavefront's work: recompress it with bgzip), a member whose CRC32 or ISIZE does not check (with
         the member's file offset), a last member that is cut short.  A missing EOF member is accepted, as htslib accepts it with a
-        warning.  A refused line's number is that of the decompressed text."""
+        warning.  A refused line's number is that of the decompressed text.
+        ``region=(name, beg, end)``, 0-based and half-open, reads one BGZF file at random through ``path + ".tbi"`` (``write(...,
+        compress=True, index=True)``, ``tabix_index``): the index is read on the host, the chunks of the region's bins that end above
+        the linear index's offset are taken, only the members they span are inflated, only the text between a chunk's begin and end is
+        parsed, and the rows that overlap the region are kept -- ``read(path, ref).select(mask)`` of the whole file, for the price of
+        the region.  The result's ``members_inflated`` says how many of the file's members were touched.  A name the index
+        does not hold gives an empty table; a missing .tbi, a plain-text path and a list of several paths raise MdkError."""
         dev = _parse_device(device)
         if not isinstance(reference, Reference):
             raise MdkError("Calls.read needs a Reference: a bedGraph line's strand and context come from its bases")
-        paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
         block_bytes = _parse_block_bytes(block_bytes)
+        if region is not None:
+            region, stats = _region_check(region), {}
+            if not isinstance(paths, (str, bytes, os.PathLike)):
+                raise MdkError("a region is read from one file: every file has an index of its own")
+            text = reference._renderer(device)
+            cols = _parse_cat(_parse_region(text.L, text, paths, PARSE_BEDGRAPH, CALL_COLUMNS, dev, block_bytes, region, stats), CALL_COLUMNS, dev)
+            names = list(reference.contigs)
+            keep = (cols["contig"] == (names.index(region[0]) if region[0] in names else -1)) & (cols["start"] < region[2]) & (cols["end"] > region[1])
+            cols = {n: t[keep].contiguous() for n, t in cols.items()}
+            c = cls(names, cols, merged=False, contexts_on=_contexts_present(cols["context"]) if contexts_on is None else contexts_on)
+            c._text, c.members_inflated = text, stats["members_inflated"]
+            return c
+        paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
         text = reference._renderer(device)
         pieces = []
         for p in paths:
@@ -1683,28 +2047,47 @@ class Cytosines(_Columns):
         columns hold now.  ``compress=True``: the bytes of the BGZF file, as ``Calls.render``.  CPU tensors raise MdkError."""
         return self._render(TEXT_CYTOSINE_REPORT, None, b"", block_rows, compress)
 
-    def write(self, prefix, directory=None, block_rows=None, compress=False):
+    def write(self, prefix, directory=None, block_rows=None, compress=False, index=False):
         """<prefix>.cytosine_report.txt as the command writes it, in ``directory`` if given; blocks as ``Calls.write``.  ``compress=True``
-        writes <prefix>.cytosine_report.txt.gz, BGZF compressed on the device as ``Calls.write`` does.  Returns the path."""
+        writes <prefix>.cytosine_report.txt.gz, BGZF compressed on the device as ``Calls.write`` does; ``index=True`` with it writes
+        <prefix>.cytosine_report.txt.gz.tbi next to it (columns 1 and 2, no line skipped), made on the device from the text on its way to
+        the deflate, and refuses what ``Calls.write`` refuses.  Returns the path."""
         name = f"{prefix}.cytosine_report.txt" + (".gz" if compress else "")
-        return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows, compress)
+        if index and not compress:
+            raise MdkError("index=True needs compress=True: a tabix index is the index of a BGZF file")
+        return self._write_file(os.path.join(directory, name) if directory is not None else name, TEXT_CYTOSINE_REPORT, None, b"", block_rows, compress,
+                                _tabix_conf("cytosine_report", 0) if index else None)
 
     @classmethod
-    def read(cls, path, contigs, device=0, contexts_on=None, block_bytes=None):
+    def read(cls, path, contigs, device=0, contexts_on=None, block_bytes=None, region=None):
         """The rows of a <prefix>.cytosine_report.txt as a Cytosines on ``device``, parsed there (csrc/mdk_parse.hip), in the file's order.
         ``contigs`` is the list of names the lines' first column is looked up in (a session result's ``contigs``, a ``Reference``'s); no
         reference is needed: strand, context and trinucleotide are in the file.  ``contexts_on`` defaults to the contexts that have rows.
         Pieces, refusals and errors as ``Calls.read``, BGZF files (``write(compress=True)``'s, bgzip's) and what is refused of .gz files
         included; there is no CPU path.  Reports of several samples
-        read this way stack as a session's do: ``torch.stack([a.nmeth, b.nmeth])``."""
+        read this way stack as a session's do: ``torch.stack([a.nmeth, b.nmeth])``.  ``region=(name, beg, end)``, 0-based and half-open:
+        the cytosines of that region alone, read through ``path + ".tbi"`` as ``Calls.read`` reads a region (a cytosine at ``pos`` is the
+        interval [pos - 1, pos)); ``members_inflated`` as there."""
         dev = _parse_device(device)
         block_bytes = _parse_block_bytes(block_bytes)
         contigs = list(contigs)
         L = _text_lib()
         text = _TextRenderer(L, int(device), contigs)
-        cols = _parse_cat(_parse_file(L, text, os.fspath(path), PARSE_CYTOSINE_REPORT, CYTOSINE_COLUMNS, dev, block_bytes), CYTOSINE_COLUMNS, dev)
-        cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
+        stats = {}
+        if region is not None:
+            region = _region_check(region)
+            if not isinstance(path, (str, bytes, os.PathLike)):
+                raise MdkError("a region is read from one file: every file has an index of its own")
+            cols = _parse_cat(_parse_region(L, text, path, PARSE_CYTOSINE_REPORT, CYTOSINE_COLUMNS, dev, block_bytes, region, stats), CYTOSINE_COLUMNS, dev)
+            cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
+            keep = (cols["contig"] == (contigs.index(region[0]) if region[0] in contigs else -1)) & (cols["pos"] - 1 < region[2]) & (cols["pos"] > region[1])
+            cols = {n: t[keep].contiguous() for n, t in cols.items()}
+        else:
+            cols = _parse_cat(_parse_file(L, text, os.fspath(path), PARSE_CYTOSINE_REPORT, CYTOSINE_COLUMNS, dev, block_bytes), CYTOSINE_COLUMNS, dev)
+            cols["trinucleotide"] = cols["trinucleotide"].reshape(-1, 3)
         c = cls(contigs, cols)
+        if stats:
+            c.members_inflated = stats["members_inflated"]
         c.contexts_on = _contexts_present(cols["context"]) if contexts_on is None else tuple(contexts_on)
         c._text = text
         return c
