@@ -15,6 +15,7 @@ import ctypes as C
 import os
 import struct
 import subprocess
+import threading
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -23,6 +24,7 @@ BUILD = Path(os.environ["MDK_BUILD_DIR"]) if os.environ.get("MDK_BUILD_DIR") els
 LIB_HIP = BUILD / "libmdk_hip.so"
 LIB_EXTRACT = BUILD / "libmdk_extract.so"
 LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
+LIB_STATS = BUILD / "libmdk_stats.so"                          # the replicates' F test: likewise, loaded at the first diff_replicates call
 CLI = BUILD / "MethylDackel"
 
 CHUNK_NOREF, CHUNK_FOREIGN, CHUNK_BED = 1, 2, 4
@@ -2290,9 +2292,59 @@ class Cohort:
         cols.update(zip((name for name, _ in DIFF_RESULT_COLUMNS), out))
         return Diff(self.contigs, cols, merged=self.merged)
 
+    def diff_replicates(self, a, b, min_dispersion=1.0):
+        """``diff`` for groups of REPLICATES, which is what most experiments have: the quasi-binomial F test of ``diff_replicates`` in
+        the place of Fisher's test of the pooled table, which takes every read of a group for an independent draw and rejects far too
+        often when the samples of a group differ by more than that.  ``a`` and ``b`` as for ``diff``.  A ``ReplicateDiff`` with this
+        table's site columns (the same tensors), the groups' pooled counts and ``meth_diff`` as ``diff`` gives them, ``pvalue`` the F
+        test's, and ``df``, ``dispersion`` and ``statistic``.  With one sample a group there is nothing to estimate a dispersion
+        from: every site has p 1.0 and df 0, and ``diff`` is the test for that experiment."""
+        out = diff_replicates(self.nmeth, self.nunmeth, a, b, min_dispersion=min_dispersion)
+        cols = {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}
+        cols.update(zip((name for name, _ in REPLICATE_RESULT_COLUMNS), out))
+        return ReplicateDiff(self.contigs, cols, merged=self.merged)
+
 
 DIFF_SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"))
 DIFF_RESULT_COLUMNS = (("nmeth_a", "int64"), ("nunmeth_a", "int64"), ("nmeth_b", "int64"), ("nunmeth_b", "int64"), ("meth_diff", "float64"), ("pvalue", "float64"))
+
+
+def _diff_arguments(what, nmeth, nunmeth, a, b):
+    """what ``diff_counts`` and ``diff_replicates`` ask of their arguments, checked before a library is touched: (S, n, the samples'
+    marks -- 0: group a, 1: group b, -1: not used --, the matrices' device)"""
+    import torch
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    marks = [-1] * S
+    for g, (label, group) in enumerate((("a", a), ("b", b))):
+        group = [group] if isinstance(group, int) else list(group)
+        if not group:
+            raise MdkError(f"{what}: group {label} is empty")
+        for i in group:
+            if isinstance(i, bool) or not hasattr(i, "__index__") or not 0 <= int(i) < S:
+                raise MdkError(f"{what}: group {label} names sample {i!r}: the matrices hold samples 0 to {S - 1}")
+            i = int(i)
+            if marks[i] == 1 - g:
+                raise MdkError(f"{what}: sample {i} is in both groups")
+            marks[i] = g
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous, sample-major")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if t.device.type != "cuda":
+            raise MdkError(f"groups are compared on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    if nunmeth.device != dev:
+        raise MdkError(f"{what}: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    return S, n, marks, dev
 
 
 def diff_counts(nmeth, nunmeth, a, b, _text=None):
@@ -2305,39 +2357,10 @@ def diff_counts(nmeth, nunmeth, a, b, _text=None):
     coverage, 0.0 where it would be below about 1e-280).  The p-value is made of IEEE multiplications, divisions and additions in a
     fixed order (csrc/mdk_diff_core.h): the same bits on every run and every device, exact to about (4 * support + 8) * 2^-53.  A
     negative entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do
-    CPU tensors: there is no CPU path.  Not here: one-sided tests, more than two groups, over-dispersion between replicates."""
+    CPU tensors: there is no CPU path.  Not here: one-sided tests, more than two groups; the over-dispersion between replicates
+    is ``diff_replicates``'s."""
     import torch
-    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
-            raise MdkError(f"diff_counts: {name} must be a [samples, sites] tensor of int32 or int64")
-    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
-        raise MdkError(f"diff_counts: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
-    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
-    if not 1 <= S <= MAX_SAMPLES:
-        raise MdkError(f"diff_counts takes 1 to {MAX_SAMPLES} samples, not {S}")
-    if n > 1 << 30:
-        raise MdkError(f"{n} sites: more than 2^30")
-    marks = [-1] * S
-    for g, (label, group) in enumerate((("a", a), ("b", b))):
-        group = [group] if isinstance(group, int) else list(group)
-        if not group:
-            raise MdkError(f"diff_counts: group {label} is empty")
-        for i in group:
-            if isinstance(i, bool) or not hasattr(i, "__index__") or not 0 <= int(i) < S:
-                raise MdkError(f"diff_counts: group {label} names sample {i!r}: the matrices hold samples 0 to {S - 1}")
-            i = int(i)
-            if marks[i] == 1 - g:
-                raise MdkError(f"diff_counts: sample {i} is in both groups")
-            marks[i] = g
-    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
-        if not t.is_contiguous():
-            raise MdkError(f"diff_counts: {name} must be contiguous, sample-major")
-    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
-        if t.device.type != "cuda":
-            raise MdkError(f"groups are compared on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
-    dev = nmeth.device
-    if nunmeth.device != dev:
-        raise MdkError(f"diff_counts: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    S, n, marks, dev = _diff_arguments("diff_counts", nmeth, nunmeth, a, b)
     L = _text_lib()
     if _text is None:
         _text = _TextRenderer(L, dev.index or 0, [])         # this call's own: a stream and a status block, closed when the call returns
@@ -2349,6 +2372,72 @@ def diff_counts(nmeth, nunmeth, a, b, _text=None):
                         *[C.c_void_p(t.data_ptr()) for t in out])
     if rc:
         raise _rc_error("md_text_diff", rc, L.md_dev_last_error().decode())
+    return tuple(out)
+
+
+# ---- the replicates' F test (include/mdk_stats.h, csrc/mdk_qdiff.hip -> libmdk_stats.so; the rule is csrc/mdk_qdiff_core.h) ----
+REPLICATE_RESULT_COLUMNS = DIFF_RESULT_COLUMNS + (("df", "int32"), ("dispersion", "float64"), ("statistic", "float64"))
+_stats, _stats_handles = None, {}
+_stats_lock = threading.Lock()
+
+
+def lib_stats():
+    """libmdk_stats.so, loaded at the first ``diff_replicates`` call: its code object's load is paid there and by no command"""
+    global _stats
+    if _stats is None:
+        if not LIB_STATS.exists():
+            raise MdkError(f"{LIB_STATS} is missing: the statistics library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+        L = C.CDLL(str(LIB_STATS))
+        L.md_stats_last_error.restype = C.c_char_p
+        L.md_stats_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.md_stats_qdiff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 10
+        L.md_stats_close.argtypes = [C.c_void_p]; L.md_stats_close.restype = None
+        _stats = L
+    return _stats
+
+
+def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
+    """Two groups of REPLICATE samples compared site by site on the device (csrc/mdk_qdiff.hip): the quasi-binomial F test, where
+    ``diff_counts`` has Fisher's test of the pooled table.  The arguments are ``diff_counts``'s, checked as it checks them: two ``[S,
+    n]`` device tensors of one dtype, int32 or int64, contiguous, and two disjoint sequences of row indices, neither empty; rows in
+    neither are not read.  Per site a sample with ``nmeth + nunmeth == 0`` is not covered and is left out; ka and kb are the covered
+    samples of the groups, nu = ka + kb - 2.  The statistic is Pearson's chi-square of the pooled table divided by the dispersion:
+    Pearson's residuals of the covered samples around their group's pooled fraction, squared, added and divided by nu (McCullagh and
+    Nelder's estimate; methylKit's ``overdispersion="MN", test="F"`` with the score statistic in the place of the deviance), and
+    ``min_dispersion`` where that is smaller -- 1.0: replicates are never taken for less variable than independent draws.  The p-value
+    is P(F(1, nu) > statistic).  Returns nine new tensors of n entries: ``nmeth_a``, ``nunmeth_a``, ``nmeth_b``, ``nunmeth_b``
+    (int64) and ``meth_diff`` (float64) as ``diff_counts`` gives them, ``pvalue`` (float64), ``df`` (int32: nu, 0 below 1),
+    ``dispersion`` and ``statistic`` (float64); with ``steps=True`` a tenth, uint32: the terms the tail's series took.  A site with
+    nothing to test -- a group without a covered sample, nu < 1 (one sample a group), nothing or everything methylated in both -- has
+    pvalue 1.0, dispersion 1.0 and statistic 0.0.  All of it is IEEE multiplications, divisions and additions in one order
+    (csrc/mdk_qdiff_core.h): the same bits on every run and every device; the p-value's relative error is bounded by (4 steps + 12 nu +
+    32) * 2^-53 from 1e-280 up, and it is 0.0 below that.  ``min_dispersion`` is a finite float within [2^-55, 2^800].  A negative
+    entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do CPU
+    tensors: there is no CPU path.  Not here: covariates, more than two groups, one-sided tests, the deviance statistic."""
+    import torch
+    if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
+        raise MdkError(f"diff_replicates: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
+    S, n, marks, dev = _diff_arguments("diff_replicates", nmeth, nunmeth, a, b)
+    groups = [[s for s in range(S) if marks[s] == g] for g in (0, 1)]           # each ascending: the rule's visiting order
+    order = (C.c_int32 * (len(groups[0]) + len(groups[1])))(*(groups[0] + groups[1]))
+    L = lib_stats()
+    out = [torch.empty(n, dtype=getattr(torch, dt), device=dev) for _, dt in REPLICATE_RESULT_COLUMNS]
+    if steps:
+        out.append(torch.empty(n, dtype=torch.uint32, device=dev))
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    with _stats_lock:                                        # a handle per device, kept: its calls come from one thread at a time
+        h = _stats_handles.get(dev.index or 0)
+        if h is None:
+            h = C.c_void_p()
+            rc = L.md_stats_open(dev.index or 0, C.byref(h))
+            if rc:
+                raise _rc_error("md_stats_open", rc, L.md_stats_last_error().decode())
+            _stats_handles[dev.index or 0] = h
+        rc = L.md_stats_qdiff(h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(groups[0]), len(groups[1]),
+                              float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
+        detail = L.md_stats_last_error().decode() if rc else None
+    if rc:
+        raise _rc_error("md_stats_qdiff", rc, detail)
     return tuple(out)
 
 
@@ -2399,7 +2488,15 @@ class Diff(_Columns):
         not measurements: 300 bases is metilene's distance, three sites DSS's minimum.  Rows not strictly ascending in (contig,
         start), a contig index outside ``contigs``, a negative count, a count of 2^26 or more and a region whose pooled margins reach
         2^26 raise MdkError (rc -3) naming the first such row; so do CPU tensors: there is no CPU path.  Not here: smoothing, a
-        minimum length in bases (``select((r.end - r.start) >= L)`` does it), merging regions of opposite direction."""
+        minimum length in bases (``select((r.end - r.start) >= L)`` does it), merging regions of opposite direction.
+
+        On a ``ReplicateDiff`` the joining is the same -- it takes the mask and the pooled counts, whatever test made the mask --, and
+        a region's own ``pvalue`` stays Fisher's test of the pooled sums: it does not know the replicates.  The replicates' test of
+        the regions is one more call, on every sample's sums over them::
+
+            r = d.dmrs(d.qvalue() < 0.01)
+            per = [cohort.sample(i).regions(r.intervals()) for i in range(cohort.n_samples)]
+            test = mdk.diff_replicates(torch.stack([p.nmeth for p in per]), torch.stack([p.nunmeth for p in per]), a, b)"""
         import math
         import torch
         names = [n for n, _ in DIFF_SITE_COLUMNS[:3] + DIFF_RESULT_COLUMNS[:4]]
@@ -2454,6 +2551,26 @@ class Diff(_Columns):
         %.17g, which reads back to the same bits.  Returns the path."""
         with open(path, "w") as f:
             f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
+        return path
+
+
+class ReplicateDiff(Diff):
+    """What ``Cohort.diff_replicates`` returns: a ``Diff`` whose ``pvalue`` is the quasi-binomial F test's, with three columns more
+    behind it -- ``df`` (int32: the covered samples of both groups less two, 0 below 1), ``dispersion`` (float64: the estimate, or the
+    floor where that is larger) and ``statistic`` (float64: F).  The pooled counts and ``meth_diff`` are ``Cohort.diff``'s, bit for
+    bit, so ``qvalue``, ``select`` and ``dmrs`` are ``Diff``'s own, unchanged."""
+    COLUMNS = DIFF_SITE_COLUMNS + REPLICATE_RESULT_COLUMNS
+
+    def rows(self):
+        """(chrom, start, end, context, strand, nmeth_a, nunmeth_a, nmeth_b, nunmeth_b, meth_diff, pvalue, df, dispersion, statistic)
+        tuples on the host"""
+        return super().rows()
+
+    def write(self, path):
+        """the fourteen columns, tab-separated, the contig by its name, without a header; formatted on the host, the four doubles
+        with %.17g, which reads back to the same bits.  Returns the path."""
+        with open(path, "w") as f:
+            f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
         return path
 
 

@@ -1,6 +1,6 @@
 // mdk_qdiff_core.h -- two groups of REPLICATE samples compared site by site: the quasi-binomial F test of a site's counts, and nothing else.
-// The rule alone, with its host build (tools/qdiff_emu.cpp) and its tests (tests/test_qdiff_cpu.py): no kernel runs it yet, and nothing of
-// the package calls it.
+// The rule alone, with its host build (tools/qdiff_emu.cpp) and its tests (tests/test_qdiff_cpu.py); k_qdiff of csrc/mdk_qdiff.hip runs it
+// on the device (libmdk_stats.so: mdk.diff_replicates, Cohort.diff_replicates).
 //
 // It is the quasi-likelihood score test of a logistic regression with one two-level covariate (the group), the dispersion estimated as
 // McCullagh and Nelder do, from Pearson's residuals of the samples around their group's pooled fraction: the idea of methylKit's
