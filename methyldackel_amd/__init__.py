@@ -25,6 +25,7 @@ LIB_HIP = BUILD / "libmdk_hip.so"
 LIB_EXTRACT = BUILD / "libmdk_extract.so"
 LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
 LIB_STATS = BUILD / "libmdk_stats.so"                          # the replicates' F test: likewise, loaded at the first diff_replicates call
+LIB_TRACK = BUILD / "libmdk_track.so"                          # the bigWig track: likewise, loaded at the first render_bigwig / write_bigwig call
 CLI = BUILD / "MethylDackel"
 
 CHUNK_NOREF, CHUNK_FOREIGN, CHUNK_BED = 1, 2, 4
@@ -1798,6 +1799,109 @@ class Calls(_Columns):
         path."""
         return self._regions([getattr(self, name) for name, _ in CALL_COLUMNS], intervals, contexts, strand, min_depth)
 
+    # ---- the bigWig track (include/mdk_track.h, csrc/mdk_bigwig.hip -> libmdk_track.so; the rule is csrc/mdk_bigwig_core.h) ----
+    def _track_arguments(self, lengths, value, context):
+        """the checks of ``render_bigwig`` and ``write_bigwig``, made before anything is opened: (the five columns, the lengths as a C
+        array, the value's code, the device)"""
+        import torch
+        if value not in TRACK_VALUES:
+            raise MdkError(f"unknown value {value!r}: one of {', '.join(TRACK_VALUES)}")
+        if isinstance(lengths, Reference):
+            if list(lengths.contigs) != list(self.contigs):
+                raise MdkError("the reference's contigs are not the rows' contigs: its lengths would be those of other sequences")
+            lengths = lengths.lengths
+        try:
+            lengths = list(lengths)
+        except TypeError:
+            raise MdkError("lengths is a Reference, or a sequence of one int per contig") from None
+        if len(lengths) != len(self.contigs):
+            raise MdkError(f"lengths has {len(lengths)} entries, the rows have {len(self.contigs)} contigs")
+        for name, l in zip(self.contigs, lengths):
+            if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l <= 2 ** 31 - 1:
+                raise MdkError(f"the length of {name} must be an int between 0 and 2^31 - 1, not {l!r}")
+        if context is not None:
+            if context in CONTEXT_FILES:
+                context = CONTEXT_FILES.index(context)
+            if isinstance(context, bool) or context not in (0, 1, 2):
+                raise MdkError(f"unknown context {context!r}: None, one of {CONTEXT_FILES}, or an index 0 to 2")
+        cols = [getattr(self, name) for name in TRACK_COLUMNS] + [self.context]
+        dev, n = cols[0].device, int(cols[0].shape[0])
+        for t, name in zip(cols, TRACK_COLUMNS + ("context",)):
+            dt = "uint8" if name == "context" else "int32"
+            if t.device.type != "cuda":
+                raise MdkError(f"the track is made on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+            if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
+        if context is not None:
+            keep = cols[5] == context
+            cols = [t[keep].contiguous() for t in cols[:5]]
+        return cols[:5], (C.c_int64 * len(lengths))(*lengths), TRACK_VALUES[value], dev
+
+    def _track_measure(self, L, h, cols, lengths, value):
+        """md_track_bigwig_measure over the columns, under the handle's lock: the file's size"""
+        names = (C.c_char_p * len(self.contigs))(*[os.fsencode(s) for s in self.contigs])
+        size = C.c_int64()
+        rc = L.md_track_bigwig_measure(h, *[C.c_void_p(t.data_ptr()) for t in cols], int(cols[0].shape[0]), len(self.contigs), names, lengths, value, C.byref(size))
+        if rc:
+            raise _rc_error("md_track_bigwig_measure", rc, L.md_track_last_error().decode())
+        return size.value
+
+    def render_bigwig(self, lengths, value="percent", context=None):
+        """These rows as a bigWig track -- what IGV and the UCSC browser open, and what `bedGraphToBigWig` makes of the bedGraph --: the
+        file's bytes as a uint8 tensor on the columns' device, made there (csrc/mdk_bigwig.hip) by the rule of csrc/mdk_bigwig_core.h: bbi
+        version 4, sections of 1024 rows compressed as zlib streams, the R-tree index, up to eight zoom levels of 1024 * 4^k bases and the
+        total summary.  ``lengths``: a ``Reference`` over the same ``contigs``, or one int per contig (0 to 2^31 - 1): a bigWig lists
+        every contig with its length.  ``value``: "percent", (float)(100 nmeth / (nmeth + nunmeth)) as the bedGraph's fourth column, or
+        "coverage", nmeth + nunmeth.  ``context``: ``None`` takes the rows as they are; 0, 1, 2 or "CpG", "CHG", "CHH" takes that
+        context's rows.  The rows must be strictly ascending in (contig, start) and must not overlap: a session run with several
+        contexts is not, as a whole, so pass one context.  A row outside its contig, a negative count, a row without coverage under
+        "percent", rows out of order and rows that overlap raise MdkError (rc -3) naming the first such row; so do CPU tensors: there
+        is no CPU path.  The bytes are a function of the columns and the arguments alone: the same on every run and every device, and
+        those of tools/bigwig_emu.  Not here: reading a bigWig back, bigBed, compression levels, UCSC's own zoom widths."""
+        import torch
+        cols, lengths, value, dev = self._track_arguments(lengths, value, context)
+        L = lib_track()
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        with _track_lock:                                        # a handle per device, kept: the measured file stays on it until it is filled
+            h = _track_handle(L, dev.index or 0)
+            size = self._track_measure(L, h, cols, lengths, value)
+            out = torch.empty(size, dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            rc = L.md_track_bigwig_fill_range(h, C.c_void_p(out.data_ptr()), 0, size)
+            detail = L.md_track_last_error().decode() if rc else None
+        if rc:
+            raise _rc_error("md_track_bigwig_fill_range", rc, detail)
+        return out
+
+    def write_bigwig(self, path, lengths, value="percent", context=None, piece_bytes=None):
+        """``render_bigwig``'s bytes written to ``path``, the arguments as there.  The table is measured first -- all of the device work --
+        and the file is opened only then: a refused table leaves no file.  The file then passes through one device buffer of
+        ``piece_bytes`` (default 64 MiB), laid out there a piece at a time (md_track_bigwig_fill_range), each piece copied to the host
+        once and appended.  Returns the path."""
+        import torch
+        piece_bytes = int(piece_bytes or TRACK_PIECE_BYTES)
+        if not 1 <= piece_bytes <= (1 << 31) - 1:
+            raise MdkError("piece_bytes must be between 1 and 2^31 - 1")
+        cols, lengths, value, dev = self._track_arguments(lengths, value, context)
+        L = lib_track()
+        torch.cuda.current_stream(dev).synchronize()
+        with _track_lock:
+            h = _track_handle(L, dev.index or 0)
+            size = self._track_measure(L, h, cols, lengths, value)
+            piece_bytes = min(piece_bytes, max(size, 1))
+            buf, pin = torch.empty(piece_bytes, dtype=torch.uint8, device=dev), torch.empty(piece_bytes, dtype=torch.uint8, pin_memory=True)
+            torch.cuda.current_stream(dev).synchronize()
+            with open(path, "wb") as f:
+                for at in range(0, size, piece_bytes):
+                    n = min(piece_bytes, size - at)
+                    rc = L.md_track_bigwig_fill_range(h, C.c_void_p(buf.data_ptr()), at, n)
+                    if rc:
+                        raise _rc_error("md_track_bigwig_fill_range", rc, L.md_track_last_error().decode())
+                    pin[:n].copy_(buf[:n], non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+                    f.write(memoryview(pin.numpy())[:n])
+        return path
+
     @classmethod
     def read(cls, paths, reference, device=0, contexts_on=None, block_bytes=None, region=None):
         """The rows of per-cytosine bedGraph files -- what ``write`` made, last week's run, the command-line tool's output -- as a Calls on
@@ -2439,6 +2543,54 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     if rc:
         raise _rc_error("md_stats_qdiff", rc, detail)
     return tuple(out)
+
+
+# ---- the bigWig track (include/mdk_track.h, csrc/mdk_bigwig.hip -> libmdk_track.so): Calls.render_bigwig, Calls.write_bigwig ----
+TRACK_COLUMNS = ("contig", "start", "end", "nmeth", "nunmeth")
+TRACK_VALUES = {"percent": 0, "coverage": 1}                   # BW_VALUE_* of csrc/mdk_bigwig_core.h
+TRACK_PIECE_BYTES = 64 << 20
+_track, _track_handles = None, {}
+_track_lock = threading.Lock()
+
+
+def lib_track():
+    """libmdk_track.so, loaded at the first ``render_bigwig`` / ``write_bigwig`` call: its code object's load is paid there and by no command"""
+    global _track
+    if _track is None:
+        if not LIB_TRACK.exists():
+            raise MdkError(f"{LIB_TRACK} is missing: the track library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+        L = C.CDLL(str(LIB_TRACK))
+        L.md_track_last_error.restype = C.c_char_p
+        L.md_track_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.md_track_close.argtypes = [C.c_void_p]; L.md_track_close.restype = None
+        L.md_track_limits.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.md_track_bigwig_measure.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]
+        L.md_track_bigwig_fill_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        _track = L
+    return _track
+
+
+def _track_handle(L, device):
+    """the device's md_track, opened at its first use and kept; the caller holds ``_track_lock``: a handle's calls come from one thread at a time"""
+    h = _track_handles.get(device)
+    if h is None:
+        h = C.c_void_p()
+        rc = L.md_track_open(device, C.byref(h))
+        if rc:
+            raise _rc_error("md_track_open", rc, L.md_track_last_error().decode())
+        _track_handles[device] = h
+    return h
+
+
+def track_limits(device=0, max_workgroups=0, batch_sections=0):
+    """A test hook (md_track_limits): at most ``max_workgroups`` workgroups per launch and ``batch_sections`` sections per batch for the
+    bigWig calls on ``device`` from now on; 0 is the default of either.  The bytes do not depend on them."""
+    L = lib_track()
+    with _track_lock:
+        rc = L.md_track_limits(_track_handle(L, int(device)), int(max_workgroups), int(batch_sections))
+        detail = L.md_track_last_error().decode() if rc else None
+    if rc:
+        raise _rc_error("md_track_limits", rc, detail)
 
 
 def _benjamini_hochberg(p):

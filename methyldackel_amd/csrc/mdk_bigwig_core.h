@@ -1,5 +1,5 @@
-// mdk_bigwig_core.h -- a table of calls as a bigWig track: THE RULE, plain C++ for the device and the host.  Built here for the host
-// (tools/bigwig_emu.cpp); the kernels that run it are not in the tree yet, and must give the same file byte for byte.
+// mdk_bigwig_core.h -- a table of calls as a bigWig track: THE RULE, plain C++ for the device and the host.  Built for the host by
+// tools/bigwig_emu.cpp and for the device by mdk_bigwig.hip (libmdk_track.so): both must give the same file byte for byte.
 // bbi version 4, little-endian; the file's bytes are a function of the columns and the arguments alone.
 //
 // Rows.  Row i is the item [start, end) of contig `contig` with the value
@@ -340,5 +340,35 @@ static inline bw_layout bw_make_layout(const std::vector<std::string> &names, co
     lay.pieces.push_back(tail);
     lay.total = o;
     return lay;
+}
+
+// A byte range of the file.  The data sections are contiguous in the file, and so are the sections of every written level: with the sections'
+// bytes packed one behind the other in a store, in the list's order, the file is the pieces plus 1 + levels regions of that store.
+struct bw_region { int64_t at, bytes, store; };              // bytes [at, at + bytes) of the file are bytes [store, store + bytes) of the store
+struct bw_cut { int piece; size_t index; int64_t src, dst, bytes; };       // piece 1: from pieces[index].bytes, 0: from the store; src: the offset there, dst: in the range
+static inline std::vector<bw_region> bw_make_regions(const bw_layout &lay, uint64_t n_data, const bool *written, const uint64_t *zsec, const uint32_t *size) {
+    std::vector<bw_region> out;
+    int64_t store = 0; uint64_t s0 = 0;
+    for(int k = -1; k < BW_LEVELS; k++) {
+        if(k >= 0 && !written[k]) continue;
+        const uint64_t cnt = k < 0 ? n_data : zsec[k];
+        int64_t bytes = 0;
+        for(uint64_t s = s0; s < s0 + cnt; s++) bytes += size[s];
+        if(cnt) out.push_back(bw_region{lay.sec_off[(size_t)s0], bytes, store});
+        store += bytes; s0 += cnt;
+    }
+    return out;
+}
+// what makes up bytes [offset, offset + bytes) of the file, in no particular order; the cuts' bytes add up to the range's where it lies inside the file
+static inline std::vector<bw_cut> bw_cut_range(const bw_layout &lay, const std::vector<bw_region> &regions, int64_t offset, int64_t bytes) {
+    std::vector<bw_cut> out;
+    const int64_t lo = offset, hi = offset + bytes;
+    auto cut = [&](int piece, size_t index, int64_t at, int64_t len, int64_t src0) {
+        const int64_t a = std::max(lo, at), b = std::min(hi, at + len);
+        if(a < b) out.push_back(bw_cut{piece, index, src0 + (a - at), a - lo, b - a});
+    };
+    for(size_t i = 0; i < lay.pieces.size(); i++) cut(1, i, lay.pieces[i].at, (int64_t)lay.pieces[i].bytes.size(), 0);
+    for(size_t i = 0; i < regions.size(); i++) cut(0, i, regions[i].at, regions[i].bytes, regions[i].store);
+    return out;
 }
 #endif

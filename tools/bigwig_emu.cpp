@@ -1,8 +1,10 @@
-// bigwig_emu -- TEST INFRASTRUCTURE: the host build of csrc/mdk_bigwig_core.h, in the decomposition its kernels are to have: the rule walked row by
+// bigwig_emu -- TEST INFRASTRUCTURE: the host build of csrc/mdk_bigwig_core.h, in the decomposition its kernels have (csrc/mdk_bigwig.hip): the rule walked row by
 // row, bin by bin and section by section, every section through the phases of csrc/mdk_deflate_core.h lane by lane (tools/deflate_walk.h).
 // With the deflate core it makes a whole bigWig on the CPU; zlib must inflate every section (tests/test_bigwig_cpu.py).
-//   bigwig_emu [--coverage] contigs.tsv rows.tsv out.bw     contigs.tsv: name <tab> length, the list's order; rows.tsv: contig index, start,
-//                                                           end, nmeth, nunmeth per line.  A refused table: "row R: why" on stderr, exit status 3
+//   bigwig_emu [--coverage] [--pieces N] contigs.tsv rows.tsv out.bw
+//       contigs.tsv: name <tab> length, the list's order; rows.tsv: contig index, start, end, nmeth, nunmeth per line.  A refused table:
+//       "row R: why" on stderr, exit status 3.  --pieces N: the file is assembled N bytes at a time through bw_cut_range, the header's map of
+//       a byte range onto the layout's pieces and the packed sections (what md_track_bigwig_fill_range runs), in place of the plain copies
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,9 +29,13 @@ static uint32_t compress_section(const uint8_t *in, uint32_t n, uint8_t *slot, u
 }
 
 int main(int argc, char **argv) {
-    int mode = BW_VALUE_PERCENT, a0 = 1;
-    if(argc > 1 && !strcmp(argv[1], "--coverage")) { mode = BW_VALUE_COVERAGE; a0 = 2; }
-    if(argc - a0 != 3) { fprintf(stderr, "usage: bigwig_emu [--coverage] contigs.tsv rows.tsv out.bw\n"); return 2; }
+    int mode = BW_VALUE_PERCENT, a0 = 1; long long piece_bytes = 0;
+    for(;;) {
+        if(argc > a0 && !strcmp(argv[a0], "--coverage")) { mode = BW_VALUE_COVERAGE; a0++; }
+        else if(argc > a0 + 1 && !strcmp(argv[a0], "--pieces")) { piece_bytes = atoll(argv[a0 + 1]); a0 += 2; if(piece_bytes < 1) { fprintf(stderr, "bigwig_emu: --pieces takes a number of bytes, 1 or more\n"); return 2; } }
+        else break;
+    }
+    if(argc - a0 != 3) { fprintf(stderr, "usage: bigwig_emu [--coverage] [--pieces N] contigs.tsv rows.tsv out.bw\n"); return 2; }
     std::vector<std::string> names; std::vector<uint32_t> len;
     {
         FILE *f = fopen(argv[a0], "r");
@@ -122,8 +128,25 @@ int main(int argc, char **argv) {
     // ---- the file ----
     const bw_layout lay = bw_make_layout(names, len, n_data, written, zcount, zsec, entry.data(), size.data(), raw_max, total);
     std::vector<uint8_t> file((size_t)lay.total, 0);
-    for(const bw_piece &p : lay.pieces) memcpy(file.data() + p.at, p.bytes.data(), p.bytes.size());
-    for(size_t s = 0; s < sec.size(); s++) memcpy(file.data() + lay.sec_off[s], sec[s].data(), sec[s].size());
+    if(!piece_bytes) {
+        for(const bw_piece &p : lay.pieces) memcpy(file.data() + p.at, p.bytes.data(), p.bytes.size());
+        for(size_t s = 0; s < sec.size(); s++) memcpy(file.data() + lay.sec_off[s], sec[s].data(), sec[s].size());
+    } else {
+        std::vector<uint8_t> store;                                // the sections one behind the other, as the device keeps them
+        for(const std::vector<uint8_t> &s : sec) store.insert(store.end(), s.begin(), s.end());
+        const std::vector<bw_region> regions = bw_make_regions(lay, n_data, written, zsec, size.data());
+        for(int64_t at = 0; at < lay.total; at += piece_bytes) {
+            const int64_t want = std::min<int64_t>(piece_bytes, lay.total - at);
+            std::vector<uint8_t> piece((size_t)want, 0);          // a buffer of exactly the range: a cut past it is a write outside an allocation
+            int64_t got = 0;
+            for(const bw_cut &c : bw_cut_range(lay, regions, at, want)) {
+                memcpy(piece.data() + c.dst, c.piece ? lay.pieces[c.index].bytes.data() + c.src : store.data() + c.src, (size_t)c.bytes);
+                got += c.bytes;
+            }
+            if(got != want) { fprintf(stderr, "bigwig_emu: bytes [%lld, %lld) of the file are covered by %lld bytes of cuts\n", (long long)at, (long long)(at + want), (long long)got); return 1; }
+            memcpy(file.data() + at, piece.data(), (size_t)want);
+        }
+    }
     FILE *f = fopen(argv[a0 + 2], "wb");
     if(!f || fwrite(file.data(), 1, file.size(), f) != file.size() || fclose(f)) { perror(argv[a0 + 2]); return 2; }
     delete S;
