@@ -25,6 +25,7 @@ LIB_HIP = BUILD / "libmdk_hip.so"
 LIB_EXTRACT = BUILD / "libmdk_extract.so"
 LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
 LIB_STATS = BUILD / "libmdk_stats.so"                          # the replicates' F test: likewise, loaded at the first diff_replicates call
+LIB_SMOOTH = BUILD / "libmdk_smooth.so"                        # smoothing: likewise, loaded at the first smooth call
 LIB_TRACK = BUILD / "libmdk_track.so"                          # the bigWig track: likewise, loaded at the first render_bigwig / write_bigwig call
 CLI = BUILD / "MethylDackel"
 
@@ -1799,6 +1800,13 @@ class Calls(_Columns):
         path."""
         return self._regions([getattr(self, name) for name, _ in CALL_COLUMNS], intervals, contexts, strand, min_depth)
 
+    def smooth(self, half_bases=1000, min_sites=70, kernel="tricube"):
+        """``Cohort.smooth`` for this one sample: a ``Smoothed`` with ``n_samples`` 1 and these rows' ``contig``, ``start``, ``end``,
+        ``context`` and ``strand`` (the same tensors).  The rows must be strictly ascending in (contig, start): one context of a
+        session's calls, or ``merge_context`` rows of one context."""
+        out = smooth_counts(self.contig, self.start, self.nmeth.unsqueeze(0), self.nunmeth.unsqueeze(0), half_bases, min_sites, kernel)
+        return Smoothed(self.contigs, {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}, *out, half_bases, min_sites, kernel, merged=self.merged)
+
     # ---- the bigWig track (include/mdk_track.h, csrc/mdk_bigwig.hip -> libmdk_track.so; the rule is csrc/mdk_bigwig_core.h) ----
     def _track_arguments(self, lengths, value, context):
         """the checks of ``render_bigwig`` and ``write_bigwig``, made before anything is opened: (the five columns, the lengths as a C
@@ -2408,6 +2416,16 @@ class Cohort:
         cols.update(zip((name for name, _ in REPLICATE_RESULT_COLUMNS), out))
         return ReplicateDiff(self.contigs, cols, merged=self.merged)
 
+    def smooth(self, half_bases=1000, min_sites=70, kernel="tricube"):
+        """Every sample's counts smoothed along the genome, the step between ``unite`` and a test or a plot at low coverage -- what
+        bsseq's BSmooth and DSS's ``smoothing=TRUE`` do first: a site's window reaches at least ``half_bases`` to either side AND holds
+        at least ``min_sites`` sites of its contig (BSmooth's ``h`` and ``ns``; all of a shorter contig), every row of the window
+        weighs by the tricube kernel of its distance (``kernel="flat"``: 1, a moving sum), and a sample's ``level`` is its weighted
+        methylated count over its weighted depth.  A ``Smoothed`` with this table's site columns (the same tensors), made on the device
+        by ``smooth_counts``, which documents the rule."""
+        out = smooth_counts(self.contig, self.start, self.nmeth, self.nunmeth, half_bases, min_sites, kernel)
+        return Smoothed(self.contigs, {name: getattr(self, name) for name, _ in SITE_COLUMNS}, *out, half_bases, min_sites, kernel, merged=self.merged)
+
 
 DIFF_SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"))
 DIFF_RESULT_COLUMNS = (("nmeth_a", "int64"), ("nunmeth_a", "int64"), ("nmeth_b", "int64"), ("nunmeth_b", "int64"), ("meth_diff", "float64"), ("pvalue", "float64"))
@@ -2543,6 +2561,158 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     if rc:
         raise _rc_error("md_stats_qdiff", rc, detail)
     return tuple(out)
+
+
+# ---- smoothing (include/mdk_smooth.h, csrc/mdk_smooth.hip -> libmdk_smooth.so; the rule is csrc/mdk_smooth_core.h) ----
+SMOOTH_KERNELS = {"tricube": 0, "flat": 1}                     # SMO_* of csrc/mdk_smooth_core.h
+_smooth, _smooth_handles = None, {}
+_smooth_lock = threading.Lock()
+
+
+def lib_smooth():
+    """libmdk_smooth.so, loaded at the first ``smooth`` call: its code object's load is paid there and by no command"""
+    global _smooth
+    if _smooth is None:
+        if not LIB_SMOOTH.exists():
+            raise MdkError(f"{LIB_SMOOTH} is missing: the smoothing library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+        L = C.CDLL(str(LIB_SMOOTH))
+        L.md_smooth_last_error.restype = C.c_char_p
+        L.md_smooth_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.md_smooth_run.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+        L.md_smooth_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.md_smooth_close.argtypes = [C.c_void_p]; L.md_smooth_close.restype = None
+        _smooth = L
+    return _smooth
+
+
+def _smooth_handle(L, device):
+    """the device's md_smooth, opened at its first use and kept; the caller holds ``_smooth_lock``: a handle's calls come from one thread at a time"""
+    h = _smooth_handles.get(device)
+    if h is None:
+        h = C.c_void_p()
+        rc = L.md_smooth_open(device, C.byref(h))
+        if rc:
+            raise _rc_error("md_smooth_open", rc, L.md_smooth_last_error().decode())
+        _smooth_handles[device] = h
+    return h
+
+
+def smooth_limits(device=0, tile_sites=0, chunk_sites=0, sample_batch=0, max_workgroups=0):
+    """A test hook (md_smooth_limits): the sites of a workgroup's tile, the rows of a chunk it stages, the samples of a batch and the most
+    workgroups of a launch for the smooth calls on ``device`` from now on; 0 is the default of each.  The results do not depend on them."""
+    L = lib_smooth()
+    with _smooth_lock:
+        rc = L.md_smooth_limits(_smooth_handle(L, int(device)), int(tile_sites), int(chunk_sites), int(sample_batch), int(max_workgroups))
+        detail = L.md_smooth_last_error().decode() if rc else None
+    if rc:
+        raise _rc_error("md_smooth_limits", rc, detail)
+
+
+def _smooth_arguments(contig, start, nmeth, nunmeth, half_bases, min_sites, kernel):
+    """what ``smooth_counts`` asks of its arguments, checked before the library is touched, the way ``_diff_arguments`` checks: (S, n, the
+    kernel's code, the tensors' device)"""
+    import torch
+    what = "smooth_counts"
+    for name, v, lo, hi in (("half_bases", half_bases, 0, 1 << 20), ("min_sites", min_sites, 1, 1 << 16)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise MdkError(f"{what}: {name} must be an integer within {lo} and {hi}, not {v!r}")
+    if not isinstance(kernel, str) or kernel not in SMOOTH_KERNELS:
+        raise MdkError(f"{what}: unknown kernel {kernel!r}: one of {', '.join(SMOOTH_KERNELS)}")
+    for name, t in (("contig", contig), ("start", start)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32:
+            raise MdkError(f"{what}: {name} must be a tensor of int32, one entry per site")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if contig.shape != (n,) or start.shape != (n,):
+        raise MdkError(f"{what}: the matrices hold {n} sites, contig {tuple(contig.shape)} and start {tuple(start.shape)}")
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    tensors = (("contig", contig), ("start", start), ("nmeth", nmeth), ("nunmeth", nunmeth))
+    for name, t in tensors:
+        if not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous" + (", sample-major" if t.dim() == 2 else ""))
+    for name, t in tensors:
+        if t.device.type != "cuda":
+            raise MdkError(f"counts are smoothed on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    for name, t in tensors:
+        if t.device != dev:
+            raise MdkError(f"{what}: nmeth is on {dev}, {name} on {t.device}")
+    return S, n, SMOOTH_KERNELS[kernel], dev
+
+
+def smooth_counts(contig, start, nmeth, nunmeth, half_bases=1000, min_sites=70, kernel="tricube"):
+    """Kernel-weighted methylation levels of every site, per sample, on the device (csrc/mdk_smooth.hip).  ``contig`` and ``start`` are
+    int32 device tensors of n sites, strictly ascending in (contig, start); ``nmeth`` and ``nunmeth`` two ``[S, n]`` device tensors of one
+    dtype, int32 or int64, contiguous, row s the counts of sample s.  The window of site i reaches at least ``half_bases`` (0 to 2^20) to
+    either side and holds at least ``min_sites`` (1 to 2^16) sites: with k = min(min_sites, the sites of i's contig) and d_k the distance
+    to i's k-th nearest site of the contig (i itself the first), half = max(half_bases, d_k), and the window's rows are those of the
+    contig within half of start[i]; a window never crosses a contig.  A row at distance d weighs (1 - (d / half)^3)^3 (``"tricube"``; 0
+    at d = half, 1 where half is 0) or 1 (``"flat"``).  Returns four new tensors: ``level`` and ``depth`` (float64 ``[S, n]``: the
+    weighted methylated count over the weighted depth -- NaN where that depth is 0 --, and the weighted depth), ``nsites`` and ``half``
+    (int32 ``[n]``: the window's rows and its half-width).  IEEE multiplications, divisions and additions in one order, the window's
+    rows ascending (csrc/mdk_smooth_core.h): the same bits on every run, every device and every blocking of the kernels; with the flat
+    kernel the sums are exact integers and level the correctly rounded quotient, with tricube level is within (2 nsites + 2) * 2^-53 of
+    exact arithmetic over the weights.  Rows out of order, a negative contig or start, a negative entry and an entry of 2^26 or more
+    (``diff_counts``' limit) raise MdkError (rc -3) naming the first such site; so do CPU tensors: there is no CPU path.  Not here:
+    local linear or quadratic fits (BSmooth's degree 2), other kernels, windows across contigs."""
+    import torch
+    S, n, code, dev = _smooth_arguments(contig, start, nmeth, nunmeth, half_bases, min_sites, kernel)
+    L = lib_smooth()
+    level, depth = (torch.empty((S, n), dtype=torch.float64, device=dev) for _ in range(2))
+    nsites, half = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+    with _smooth_lock:                                       # a handle per device, kept: its calls come from one thread at a time
+        h = _smooth_handle(L, dev.index or 0)
+        rc = L.md_smooth_run(h, C.c_void_p(contig.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()),
+                             nmeth.element_size(), S, n, int(half_bases), int(min_sites), code, *[C.c_void_p(t.data_ptr()) for t in (level, depth, nsites, half)])
+        detail = L.md_smooth_last_error().decode() if rc else None
+    if rc:
+        raise _rc_error("md_smooth_run", rc, detail)
+    return level, depth, nsites, half
+
+
+class Smoothed:
+    """What ``Cohort.smooth`` and ``Calls.smooth`` return, on the table's device: ``contigs``, the table's site columns (the same
+    tensors: ``contig``, ``start``, ``end``, ``context``, ``strand``, and a cohort's ``nsamples``), ``level`` and ``depth`` (float64
+    ``[S, n]``), ``nsites`` and ``half`` (int32 ``[n]``) as ``smooth_counts`` gives them, and the parameters ``half_bases``,
+    ``min_sites`` and ``kernel`` they were made with.  ``level`` is NaN where a sample has no depth in the whole window; NaN compares
+    false, so a threshold on a statistic made of levels passes such sites over."""
+
+    def __init__(self, contigs, columns, level, depth, nsites, half, half_bases, min_sites, kernel, merged=False):
+        self.contigs = contigs
+        self._site_columns = tuple(columns)
+        for name, t in columns.items():
+            setattr(self, name, t)
+        self.level, self.depth, self.nsites, self.half = level, depth, nsites, half
+        self.half_bases, self.min_sites, self.kernel = int(half_bases), int(min_sites), kernel
+        self.merged = bool(merged)
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    @property
+    def n_samples(self):
+        return int(self.level.shape[0])
+
+    def select(self, index):
+        """a copy with the sites ``column[index]`` (a boolean mask, an index tensor, a slice): of the site columns, of ``nsites`` and
+        ``half``, and of ``level`` and ``depth`` along their site axis.  The values stay those of the whole table's windows"""
+        cols = {name: getattr(self, name)[index].contiguous() for name in self._site_columns}
+        return Smoothed(self.contigs, cols, self.level[:, index].contiguous(), self.depth[:, index].contiguous(), self.nsites[index].contiguous(),
+                        self.half[index].contiguous(), self.half_bases, self.min_sites, self.kernel, self.merged)
+
+    def rows(self):
+        """(chrom, start, end, nsites, half, (level, depth) of sample 0, of sample 1, ...) tuples on the host"""
+        cols = [getattr(self, n).cpu().tolist() for n in ("contig", "start", "end", "nsites", "half")]
+        lv, dp = self.level.t().cpu().tolist(), self.depth.t().cpu().tolist()
+        return [(self.contigs[c], a, b, k, h) + tuple(zip(ll, dd)) for (c, a, b, k, h), ll, dd in zip(zip(*cols), lv, dp)]
 
 
 # ---- the bigWig track (include/mdk_track.h, csrc/mdk_bigwig.hip -> libmdk_track.so): Calls.render_bigwig, Calls.write_bigwig ----
