@@ -8,7 +8,7 @@ B      := methyldackel_amd/_build
 CFLAGS ?= -O2 -g -Wall -Wextra -Wno-unused-parameter -Wno-sign-compare -fPIC -pthread
 HOSTSRC := methyldackel_amd/csrc/host/mdk_io.c methyldackel_amd/csrc/host/mdk_fasta.c methyldackel_amd/csrc/host/mdk_bigwig.c methyldackel_amd/csrc/host/mdk_mbias.c methyldackel_amd/csrc/host/mdk_mergecontext.c methyldackel_amd/csrc/host/mdk_plan.c methyldackel_amd/csrc/host/mdk_pipeline.c methyldackel_amd/csrc/host/mdk_emit.c methyldackel_amd/csrc/host/mdk_extract.c methyldackel_amd/csrc/host/mdk_session.c methyldackel_amd/csrc/host/mdk_cmd_mbias.c methyldackel_amd/csrc/host/mdk_cmd_perread.c methyldackel_amd/csrc/host/mdk_affinity.c methyldackel_amd/csrc/host/mdk_ranks.c methyldackel_amd/csrc/host/mdk_reference.c
 
-all: $(B)/libmdk_hip.so $(B)/libmdk_extract.so $(B)/libmdk_index.so $(B)/libmdk_stats.so $(B)/libmdk_track.so $(B)/libmdk_smooth.so $(B)/MethylDackel tools oracle
+all: $(B)/libmdk_hip.so $(B)/libmdk_extract.so $(B)/libmdk_index.so $(B)/libmdk_stats.so $(B)/libmdk_track.so $(B)/libmdk_smooth.so $(B)/libmdk_cohort.so $(B)/MethylDackel tools oracle
 
 # -fgpu-rdc: the sources become ONE code object; the runtime loads a code object at the first use of one of its kernels and each load
 # costs the command ~30 ms of start-up (three of them did: pileup, preparation, inflate)
@@ -46,7 +46,12 @@ $(B)/libmdk_smooth.so: methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csr
 	@mkdir -p $(B)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_smooth.hip
 
-tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
+# the united table as text and back: a library of its own in the same way (loaded at the first Cohort.write / render / read call)
+$(B)/libmdk_cohort.so: methyldackel_amd/csrc/mdk_cohort.hip methyldackel_amd/csrc/mdk_cohort_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_parse_core.h include/mdk_cohort.h
+	@mkdir -p $(B)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_cohort.hip
+
+tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/cohort_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
 	@mkdir -p tools/_build
 	$(CC) -O2 -g -Wall -shared -fPIC -Iinclude -o $@ tools/piece_standin.c -lz
@@ -98,6 +103,9 @@ tools/_build/dmr_emu: tools/dmr_emu.cpp methyldackel_amd/csrc/mdk_dmr_core.h met
 tools/_build/smooth_emu: tools/smooth_emu.cpp methyldackel_amd/csrc/mdk_smooth_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -ffp-contract=off -o $@ tools/smooth_emu.cpp -Imethyldackel_amd/csrc
+tools/_build/cohort_emu: tools/cohort_emu.cpp methyldackel_amd/csrc/mdk_cohort_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_parse_core.h
+	@mkdir -p tools/_build
+	g++ -O2 -Wall -o $@ tools/cohort_emu.cpp -Imethyldackel_amd/csrc
 tools/_build/smooth_bench: tools/smooth_bench.hip methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/smooth_bench.hip

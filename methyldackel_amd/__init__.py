@@ -12,6 +12,7 @@ pipeline of ``extractCalls`` (reference extract.c:247-560).
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 import struct
 import subprocess
@@ -26,7 +27,8 @@ LIB_EXTRACT = BUILD / "libmdk_extract.so"
 LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
 LIB_STATS = BUILD / "libmdk_stats.so"                          # the replicates' F test: likewise, loaded at the first diff_replicates call
 LIB_SMOOTH = BUILD / "libmdk_smooth.so"                        # smoothing: likewise, loaded at the first smooth call
-LIB_TRACK = BUILD / "libmdk_track.so"                          # the bigWig track: likewise, loaded at the first render_bigwig / write_bigwig call
+LIB_COHORT = BUILD / "libmdk_cohort.so"                        # the united table as text: likewise, loaded at the first Cohort.write / render / read call
+LIB_TRACK = BUILD / "libmdk_track.so"                         # the bigWig track: likewise, loaded at the first render_bigwig / write_bigwig call
 CLI = BUILD / "MethylDackel"
 
 CHUNK_NOREF, CHUNK_FOREIGN, CHUNK_BED = 1, 2, 4
@@ -2349,15 +2351,18 @@ class Cohort:
     ``contig``, ``start``, ``end`` (int32), ``context`` (uint8) and ``strand`` (int8) describe the site as a Calls row does; ``nsamples``
     (int32) is the number of samples that hold it after the depth cut; ``nmeth`` and ``nunmeth`` are int32 matrices ``[S, n]``, row s the
     counts of sample s, zeros where it does not hold the site.  ``contigs`` and ``merged`` are the samples', ``contexts_on`` the union of
-    theirs; ``n_union`` is the number of sites any sample holds, which ``min_samples=1`` would have given."""
+    theirs; ``n_union`` is the number of sites any sample holds, which ``min_samples=1`` would have given.  ``names`` is a tuple of S
+    sample names (1 to 255 bytes of 0x21 to 0x7e each, no two alike) or None: ``unite`` leaves it None, ``select`` carries it, ``read``
+    sets it from the file, and ``write`` puts it into the file's second line."""
 
-    def __init__(self, contigs, columns, nmeth, nunmeth, merged=False, contexts_on=(0, 1, 2), n_union=None):
+    def __init__(self, contigs, columns, nmeth, nunmeth, merged=False, contexts_on=(0, 1, 2), n_union=None, names=None):
         self.contigs = contigs
         for name, _ in SITE_COLUMNS:
             setattr(self, name, columns[name])
         self.nmeth, self.nunmeth = nmeth, nunmeth
         self.merged, self.contexts_on = bool(merged), tuple(contexts_on)
         self.n_union = len(self) if n_union is None else int(n_union)
+        self.names = None if names is None else _cohort_sample_names(names, int(nmeth.shape[0]))
         self._text = None
 
     def __len__(self):
@@ -2371,7 +2376,7 @@ class Cohort:
         """a copy with the sites ``column[index]`` (a boolean mask, an index tensor, a slice): of the site columns, and of the matrices
         along their site axis"""
         cols = {name: getattr(self, name)[index].contiguous() for name, _ in SITE_COLUMNS}
-        c = Cohort(self.contigs, cols, self.nmeth[:, index].contiguous(), self.nunmeth[:, index].contiguous(), self.merged, self.contexts_on, self.n_union)
+        c = Cohort(self.contigs, cols, self.nmeth[:, index].contiguous(), self.nunmeth[:, index].contiguous(), self.merged, self.contexts_on, self.n_union, self.names)
         c._text = self._text
         return c
 
@@ -2425,6 +2430,188 @@ class Cohort:
         by ``smooth_counts``, which documents the rule."""
         out = smooth_counts(self.contig, self.start, self.nmeth, self.nunmeth, half_bases, min_sites, kernel)
         return Smoothed(self.contigs, {name: getattr(self, name) for name, _ in SITE_COLUMNS}, *out, half_bases, min_sites, kernel, merged=self.merged)
+
+    # ---- the table as text and back (include/mdk_cohort.h, csrc/mdk_cohort.hip -> libmdk_cohort.so; the formats are csrc/mdk_cohort_core.h's) ----
+    def _text_arguments(self, fmt, names, piece_bytes):
+        """what ``write`` and ``render`` ask, checked before the library is touched or a file opened: (format code, header bytes, piece_bytes, device)"""
+        import torch
+        if not isinstance(fmt, str) or fmt not in COHORT_FORMATS:
+            raise MdkError(f"unknown format {fmt!r}: one of {', '.join(COHORT_FORMATS)}")
+        S, n = int(self.nmeth.shape[0]) if self.nmeth.dim() == 2 else -1, len(self)
+        if not 1 <= S <= MAX_SAMPLES:
+            raise MdkError(f"a table is written with 1 to {MAX_SAMPLES} samples: nmeth must be a [samples, sites] tensor")
+        names = _cohort_sample_names(names if names is not None else self.names if self.names is not None else [f"s{i}" for i in range(S)], S)
+        piece_bytes = int(piece_bytes or COHORT_PIECE_BYTES)
+        if not 1 <= piece_bytes <= (1 << 31) - 1:
+            raise MdkError("piece_bytes must be between 1 and 2^31 - 1")
+        tensors = [(name, getattr(self, name), dt, (n,)) for name, dt in SITE_COLUMNS] + [("nmeth", self.nmeth, "int32", (S, n)), ("nunmeth", self.nunmeth, "int32", (S, n))]
+        for name, t, dt, shape in tensors:
+            if t.device.type != "cuda":
+                raise MdkError(f"text is made on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+        dev = self.nmeth.device
+        for name, t, dt, shape in tensors:
+            if t.device != dev or t.dtype != getattr(torch, dt) or tuple(t.shape) != shape or not t.is_contiguous():
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor of shape {shape} on {dev}")
+        if n > 1 << 30:
+            raise MdkError(f"{n} sites: more than 2^30")
+        return COHORT_FORMATS[fmt], _cohort_header(fmt, names, self.merged, self.contexts_on, self.n_union), piece_bytes, dev
+
+    def _text_stream(self, fmt, names, piece_bytes, compress, opened, sink):
+        """the table's text, block by block: ``opened()`` is called once the table is measured and no row refused, then ``sink(t)`` for the
+        header and for every block -- ``t`` a uint8 tensor on the device that is the library's one buffer (or its BGZF members): the sink
+        uses it before it returns"""
+        import torch
+        code, head, piece_bytes, dev = self._text_arguments(fmt, names, piece_bytes)
+        S, n = self.n_samples, len(self)
+        L = lib_cohort()
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        with _cohort_lock:                                       # a handle per device, kept: its calls come from one thread at a time
+            h = _cohort_handle(L, dev.index or 0, self.contigs)
+            sites = md_cohort_sites(*[C.c_void_p(getattr(self, name).data_ptr()) for name, _ in SITE_COLUMNS])
+            total = C.c_int64()
+            rc = L.md_cohort_measure(h, code, C.byref(sites), C.c_void_p(self.nmeth.data_ptr()), C.c_void_p(self.nunmeth.data_ptr()), S, n, C.byref(total))
+            if rc:
+                raise _rc_error("md_cohort_measure", rc, L.md_cohort_last_error().decode())
+            opened()
+            emit = (lambda t: sink(bgzf_compress(t, eof=False))) if compress else sink
+            emit(torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
+            buf, r0 = None, 0
+            while r0 < n:
+                r1, size = C.c_int64(), C.c_int64()
+                rc = L.md_cohort_cut(h, r0, piece_bytes, C.byref(r1), C.byref(size))
+                if rc:
+                    raise _rc_error("md_cohort_cut", rc, L.md_cohort_last_error().decode())
+                if buf is None or buf.numel() < size.value:
+                    buf = None
+                    buf = torch.empty(max(size.value, min(piece_bytes, total.value)), dtype=torch.uint8, device=dev)
+                    torch.cuda.current_stream(dev).synchronize()
+                rc = L.md_cohort_fill(h, r0, r1.value, C.c_void_p(buf.data_ptr()), size.value)
+                if rc:
+                    raise _rc_error("md_cohort_fill", rc, L.md_cohort_last_error().decode())
+                emit(buf[:size.value])
+                torch.cuda.current_stream(dev).synchronize()     # the sink's copies have left the buffer before the next block is made in it
+                r0 = r1.value
+            if compress:
+                sink(torch.frombuffer(bytearray(BGZF_EOF), dtype=torch.uint8).to(dev))
+
+    def render(self, fmt="cohort", names=None, compress=False, piece_bytes=None):
+        """the bytes ``write`` would put into a file, as a uint8 tensor on the table's device"""
+        import torch
+        parts = []
+        self._text_stream(fmt, names, piece_bytes, compress, lambda: None, lambda t: parts.append(t.clone()))
+        return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+    def write(self, path, fmt="cohort", names=None, compress=False, piece_bytes=None):
+        """The table as a text file, made on the device (csrc/mdk_cohort.hip); returns ``path``.  ``fmt="cohort"`` is the format
+        ``Cohort.read`` takes back exactly: two ``#`` lines (the version-1 signature with the samples, ``merged``, the contexts and
+        ``n_union``; then the column names, ``NAME.nmeth`` and ``NAME.nunmeth`` per sample), then one BED-like line per site, ``0 0``
+        cells included: chrom, start, end (0-based, half open), CG|CHG|CHH, ``+``, ``-`` or ``.`` (strand 0), nsamples, then nmeth and
+        nunmeth of every sample, tab-separated.  ``fmt="methylBase"`` is write-only: the columns of methylKit's ``getData(methylBase)``
+        as ``write.table(sep="\\t", quote=FALSE, row.names=FALSE)`` lays them out -- chr, start + 1 twice, ``+`` (strand >= 0) or ``-``,
+        then coverage, numCs and numTs per sample.  ``names``: the samples' names (default ``self.names``, or ``s0`` ... ``s{S-1}``).
+        ``compress``: BGZF made on the device; the header is a member of its own, every block of ``piece_bytes`` (default 64 MiB; the
+        longest run of whole rows that fits, at least one) is deflated by ``bgzf_compress``, and one EOF member ends the file.  Plain
+        bytes depend on the table alone, compressed ones also on ``piece_bytes``; ``gzip.decompress`` of the compressed file is the
+        plain one.  A negative count, a negative contig or start, a contig index outside ``contigs``, ``end <= start`` and a context
+        above 2 raise MdkError (rc -3) naming the first such site (and sample) before the file is opened; so do CPU tensors: there is
+        no CPU path.  Rows need not ascend to be written."""
+        import torch
+        state = {"f": None, "pin": None}
+
+        def sink(t):
+            k = t.numel()
+            if not k:
+                return
+            if state["pin"] is None or state["pin"].numel() < k:
+                state["pin"] = torch.empty(k + k // 8, dtype=torch.uint8, pin_memory=True)
+            state["pin"][:k].copy_(t, non_blocking=True)
+            torch.cuda.current_stream(t.device).synchronize()
+            state["f"].write(memoryview(state["pin"].numpy())[:k])
+
+        def opened():
+            state["f"] = open(path, "wb")
+        try:
+            self._text_stream(fmt, names, piece_bytes, compress, opened, sink)
+        finally:
+            if state["f"]:
+                state["f"].close()
+        return path
+
+    @classmethod
+    def read(cls, path, contigs, device=0, block_bytes=None):
+        """A ``"cohort"`` file (``Cohort.write``) read back into a Cohort on ``device``, parsed there (k_cparse_len, k_cparse_fill):
+        every column, ``names``, ``merged``, ``contexts_on`` and ``n_union`` as they were written.  ``contigs``: the contig names the
+        file's first column is looked up in, in the order their indices shall have.  Plain text or BGZF, told apart by content as
+        ``Calls.read`` tells them; BGZF members are inflated and CRC-checked on the device.  The file goes to the device in pieces of at
+        most ``block_bytes`` bytes cut at line ends.  Strict, as ``Calls.read`` is: exactly 6 + 2S fields separated by single tabs,
+        numbers of 1 to 10 digits up to INT32_MAX, a known contig, context and strand tokens, ``nsamples <= S``, ``end > start``, lines of
+        at most 32768 bytes, one trailing ``\\r`` dropped, no further ``#`` line, and rows strictly ascending in (index in ``contigs``,
+        start) -- a refused line raises MdkError with the path, the line's number and one reason."""
+        import contextlib
+        import mmap
+        import torch
+        contigs = list(contigs)
+        block_bytes = _parse_block_bytes(block_bytes)
+        kind = _gz_kind(path)
+        if kind == "gzip":
+            raise MdkError(f"{path}: a gzip file that is not BGZF (no BC subfield in its header): one member of any length is one wavefront's work. "
+                           "Recompress it with bgzip (zcat file.gz | bgzip > file.bgz.gz), or decompress it")
+        pieces = []
+        with contextlib.ExitStack() as stack:
+            if kind == "bgzf":
+                f = stack.enter_context(open(path, "rb"))
+                buf = stack.enter_context(mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ))
+                members = _bgzf_members(path, buf)
+                S, merged, contexts_on, n_union, names, hdr = _cohort_read_header(path, kind, buf, members)
+                dev = _parse_device(device)
+                source = stack.enter_context(contextlib.closing(_bgzf_pieces(_text_lib(), path, buf, members, dev, block_bytes)))
+                number = _gz_line_number
+            else:
+                S, merged, contexts_on, n_union, names, hdr = _cohort_read_header(path, kind)
+                dev = _parse_device(device)
+                source, number = _parse_pieces(path, block_bytes), _parse_line_number
+            L = lib_cohort()
+            prev = None
+            for t, cut, at in source:
+                if at + cut <= hdr:
+                    continue
+                if kind == "bgzf":
+                    d = t
+                else:
+                    d = torch.empty(cut, dtype=torch.uint8, device=dev)
+                    d.copy_(t[:cut], non_blocking=True)
+                torch.cuda.current_stream(dev).synchronize()     # the text is complete, and the pinned buffer may take the next piece
+                if d.data_ptr() & 15:
+                    d = d.clone()
+                    torch.cuda.current_stream(dev).synchronize()
+                with _cohort_lock:
+                    h = _cohort_handle(L, dev.index or 0, contigs)
+                    rows = C.c_int64()
+                    rc = L.md_cohort_parse_measure(h, C.c_void_p(d.data_ptr()), cut, max(0, hdr - at), S, C.byref(rows))
+                    if rc:
+                        raise _rc_error("md_cohort_parse_measure", rc, L.md_cohort_last_error().decode())
+                    k = rows.value
+                    cols = {name: torch.empty(k, dtype=getattr(torch, dt), device=dev) for name, dt in SITE_COLUMNS}
+                    m, u = (torch.empty((S, k), dtype=torch.int32, device=dev) for _ in range(2))
+                    torch.cuda.current_stream(dev).synchronize()
+                    sites = md_cohort_sites(*[C.c_void_p(cols[name].data_ptr()) for name, _ in SITE_COLUMNS])
+                    rc = L.md_cohort_parse_fill(h, C.byref(sites), C.c_void_p(m.data_ptr()), C.c_void_p(u.data_ptr()), k, 0, k,
+                                                int(prev is not None), *(prev or (0, 0)))
+                    detail, off = (L.md_cohort_last_error().decode(), int(L.md_cohort_parse_error_offset(h))) if rc else (None, -1)
+                if rc:
+                    raise _rc_error("reading", rc, f"{path}, line {number(path, at + off)}: {detail}" if off >= 0 else f"{path}: {detail}")
+                if k:
+                    prev = (int(cols["contig"][-1]), int(cols["start"][-1]))
+                    pieces.append((cols, m, u))
+        if len(pieces) == 1:
+            cols, m, u = pieces[0]
+        elif pieces:
+            cols = {name: torch.cat([p[0][name] for p in pieces]) for name, _ in SITE_COLUMNS}
+            m, u = (torch.cat([p[i] for p in pieces], dim=1).contiguous() for i in (1, 2))
+        else:
+            cols = {name: torch.empty(0, dtype=getattr(torch, dt), device=dev) for name, dt in SITE_COLUMNS}
+            m, u = (torch.empty((S, 0), dtype=torch.int32, device=dev) for _ in range(2))
+        return cls(contigs, cols, m, u, merged, contexts_on, n_union, names)
 
 
 DIFF_SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"))
@@ -2676,6 +2863,132 @@ def smooth_counts(contig, start, nmeth, nunmeth, half_bases=1000, min_sites=70, 
     if rc:
         raise _rc_error("md_smooth_run", rc, detail)
     return level, depth, nsites, half
+
+
+# ---- the united table as text (include/mdk_cohort.h, csrc/mdk_cohort.hip -> libmdk_cohort.so; the formats are csrc/mdk_cohort_core.h's) ----
+COHORT_FORMATS = {"cohort": 0, "methylBase": 1}                # COH_FMT_* of csrc/mdk_cohort_core.h
+COHORT_PIECE_BYTES = 64 << 20
+COHORT_SIGNATURE = "#methyldackel_amd cohort 1"
+COHORT_SITE_NAMES = ("#chrom", "start", "end", "context", "strand", "nsamples")
+_cohort, _cohort_handles, _cohort_contigs = None, {}, {}
+_cohort_lock = threading.Lock()
+
+
+class md_cohort_sites(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in (("contig", 0), ("start", 0), ("end", 0), ("context", 0), ("strand", 0), ("nsamples", 0))]
+
+
+def lib_cohort():
+    """libmdk_cohort.so, loaded at the first ``Cohort.write`` / ``render`` / ``read`` call: its code object's load is paid there and by no command"""
+    global _cohort
+    if _cohort is None:
+        if not LIB_COHORT.exists():
+            raise MdkError(f"{LIB_COHORT} is missing: the cohort text library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+        L = C.CDLL(str(LIB_COHORT))
+        L.md_cohort_last_error.restype = C.c_char_p
+        L.md_cohort_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.md_cohort_close.argtypes = [C.c_void_p]; L.md_cohort_close.restype = None
+        L.md_cohort_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.md_cohort_names.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_int32]
+        L.md_cohort_measure.argtypes = [C.c_void_p, C.c_int, C.POINTER(md_cohort_sites), C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        L.md_cohort_cut.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.md_cohort_fill.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+        L.md_cohort_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.md_cohort_parse_fill.argtypes = [C.c_void_p, C.POINTER(md_cohort_sites), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32]
+        L.md_cohort_parse_error_offset.argtypes = [C.c_void_p]; L.md_cohort_parse_error_offset.restype = C.c_int64
+        _cohort = L
+    return _cohort
+
+
+def _cohort_handle(L, device, contigs=None):
+    """the device's md_cohort, opened at its first use and kept, with ``contigs`` as its contig names (uploaded when they change); the
+    caller holds ``_cohort_lock``: a handle's calls come from one thread at a time"""
+    h = _cohort_handles.get(device)
+    if h is None:
+        h = C.c_void_p()
+        rc = L.md_cohort_open(device, C.byref(h))
+        if rc:
+            raise _rc_error("md_cohort_open", rc, L.md_cohort_last_error().decode())
+        _cohort_handles[device] = h
+    if contigs is not None and _cohort_contigs.get(device) != tuple(contigs):
+        blobs = [str(c).encode() for c in contigs]
+        off = (C.c_uint32 * (len(blobs) + 1))(*([0] + list(itertools.accumulate(len(b) for b in blobs))))
+        _cohort_contigs.pop(device, None)
+        rc = L.md_cohort_names(h, b"".join(blobs), off, len(blobs))
+        if rc:
+            raise _rc_error("md_cohort_names", rc, L.md_cohort_last_error().decode())
+        _cohort_contigs[device] = tuple(contigs)
+    return h
+
+
+def cohort_limits(device=0, tile_sites=0, sample_block=0, max_workgroups=0):
+    """A test hook (md_cohort_limits): the sites of a tile, the samples of a block and the most workgroups of a launch for the
+    ``Cohort.write`` / ``render`` / ``read`` calls on ``device`` from now on; 0 is the default of each.  No byte and no column depends on them."""
+    L = lib_cohort()
+    with _cohort_lock:
+        rc = L.md_cohort_limits(_cohort_handle(L, int(device)), int(tile_sites), int(sample_block), int(max_workgroups))
+        detail = L.md_cohort_last_error().decode() if rc else None
+    if rc:
+        raise _rc_error("md_cohort_limits", rc, detail)
+
+
+def _cohort_sample_names(names, S):
+    """``names`` as a tuple of S sample names: 1 to 255 bytes of 0x21 to 0x7e each, no two alike"""
+    if isinstance(names, (str, bytes)) or not hasattr(names, "__iter__"):
+        raise MdkError("names must be a sequence of sample names")
+    names = tuple(names)
+    if len(names) != S:
+        raise MdkError(f"{len(names)} names for {S} samples")
+    for k, v in enumerate(names):
+        if not isinstance(v, str) or not 1 <= len(v) <= 255 or any(not 0x21 <= ord(c) <= 0x7e for c in v):
+            raise MdkError(f"the name of sample {k}, {v!r}, is not 1 to 255 bytes of 0x21 to 0x7e")
+    if len(set(names)) != S:
+        raise MdkError("two samples have the same name")
+    return names
+
+
+def _cohort_header(fmt, names, merged, contexts_on, n_union):
+    """the lines in front of a table's rows, formatted on the host"""
+    if fmt == "methylBase":
+        return ("\t".join(["chr", "start", "end", "strand"] + [f"{w}{k + 1}" for k in range(len(names)) for w in ("coverage", "numCs", "numTs")]) + "\n").encode()
+    first = "\t".join([COHORT_SIGNATURE, f"samples={len(names)}", f"merged={int(bool(merged))}", "contexts=" + ",".join(str(int(x)) for x in contexts_on), f"n_union={int(n_union)}"])
+    second = "\t".join(list(COHORT_SITE_NAMES) + [f"{v}.{w}" for v in names for w in ("nmeth", "nunmeth")])
+    return (first + "\n" + second + "\n").encode()
+
+
+def _cohort_read_header(path, kind, buf=None, members=()):
+    """the two ``#`` lines of a "cohort" file, read on the host: (S, merged, contexts_on, n_union, names, the bytes the two lines take).
+    Of a BGZF file (``buf``: its bytes, ``members``: its table) the first members are inflated here until they hold two lines, unchecked:
+    the device inflates and checks every member when the rows are read"""
+    import re
+    import zlib
+    if kind == "bgzf":
+        head = b""
+        for _, so, sl, _, _ in members:
+            if head.count(b"\n") >= 2:
+                break
+            try:
+                head += zlib.decompressobj(-15).decompress(bytes(buf[so:so + sl]))
+            except zlib.error:
+                break
+        lines = head.split(b"\n", 2)
+        first, second = (lines[0] + b"\n" if len(lines) > 1 else lines[0]), (lines[1] + b"\n" if len(lines) > 2 else lines[1] if len(lines) > 1 else b"")
+    else:
+        with open(path, "rb") as f:
+            first, second = f.readline(), f.readline()
+    m = re.fullmatch(re.escape(COHORT_SIGNATURE) + r"\tsamples=([0-9]{1,4})\tmerged=([01])\tcontexts=((?:[012](?:,[012])*)?)\tn_union=([0-9]{1,18})\r?\n", first.decode("latin-1"))
+    if not m or not 1 <= int(m.group(1)) <= MAX_SAMPLES:
+        raise MdkError(f"{path}, line 1: not the signature of a version-1 cohort file ({COHORT_SIGNATURE!r}, then samples=, merged=, contexts= and n_union=)")
+    S = int(m.group(1))
+    fields = second.decode("latin-1").rstrip("\n").rstrip("\r").split("\t") if second.endswith(b"\n") else []
+    names = [v[:-len(".nmeth")] for v in fields[6::2]]
+    if len(fields) != 6 + 2 * S or tuple(fields[:6]) != COHORT_SITE_NAMES or any(a != f"{v}.nmeth" or b != f"{v}.nunmeth" for v, a, b in zip(names, fields[6::2], fields[7::2])):
+        raise MdkError(f"{path}, line 2: the column names of {S} samples are {6 + 2 * S} fields, the six site columns and NAME.nmeth, NAME.nunmeth per sample")
+    try:
+        names = _cohort_sample_names(names, S)
+    except MdkError as e:
+        raise MdkError(f"{path}, line 2: {e}") from None
+    return S, bool(int(m.group(2))), tuple(int(x) for x in m.group(3).split(",") if x), int(m.group(4)), names, len(first) + len(second)
 
 
 class Smoothed:
