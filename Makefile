@@ -23,33 +23,25 @@ $(B)/libmdk_extract.so: $(HOSTSRC) methyldackel_amd/csrc/host/mdk_io.h methyldac
 $(B)/MethylDackel: methyldackel_amd/csrc/host/main.c $(B)/libmdk_extract.so
 	$(CC) $(CFLAGS) -Iinclude -o $@ methyldackel_amd/csrc/host/main.c -L$(B) -lmdk_extract -lmdk_hip -Wl,-rpath,'$$ORIGIN' -lz -lm
 
-# the tabix index's device code: a library of its own -- one source, one code object, no link to the two above (loaded at the first index call)
-$(B)/libmdk_index.so: methyldackel_amd/csrc/mdk_tabix.hip methyldackel_amd/csrc/mdk_tabix_core.h methyldackel_amd/csrc/mdk_parse_core.h include/mdk_index.h
+# the side libraries: each a library of its own -- one source, one code object, no link to the two above or to each other --, loaded at the
+# first call that needs it.  $(1): the library, $(2): its source in csrc/, $(3): the headers it is made of beside csrc/mdk_side.hpp, the
+# host layer each of them holds a copy of.  No flag that relaxes the arithmetic: the rules' bits are the host's
+CSRC := methyldackel_amd/csrc
+define side_lib
+$(B)/libmdk_$(1).so: $(CSRC)/$(2) $(CSRC)/mdk_side.hpp $(3)
 	@mkdir -p $(B)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_tabix.hip
-
-# the replicates' F test: a library of its own in the same way (loaded at the first diff_replicates call).  No flag that relaxes the
-# arithmetic: the rule's bits are the host's
-$(B)/libmdk_stats.so: methyldackel_amd/csrc/mdk_qdiff.hip methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h include/mdk_stats.h
-	@mkdir -p $(B)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_qdiff.hip
-
-# the bigWig track: a library of its own in the same way (loaded at the first render_bigwig / write_bigwig call).  No flag that relaxes
-# the arithmetic: mdk_bigwig_core.h's BW_NO_CONTRACT keeps the products unfused, and the file's bytes are the host build's
-$(B)/libmdk_track.so: methyldackel_amd/csrc/mdk_bigwig.hip methyldackel_amd/csrc/mdk_bigwig_core.h methyldackel_amd/csrc/mdk_deflate_core.h include/mdk_track.h
-	@mkdir -p $(B)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_bigwig.hip
-
-# smoothing: a library of its own in the same way (loaded at the first smooth call).  No flag that relaxes the arithmetic:
-# mdk_smooth_core.h's MDK_SMO_NO_CONTRACT keeps the products unfused, and the rule's bits are the host's
-$(B)/libmdk_smooth.so: methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
-	@mkdir -p $(B)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_smooth.hip
-
-# the united table as text and back: a library of its own in the same way (loaded at the first Cohort.write / render / read call)
-$(B)/libmdk_cohort.so: methyldackel_amd/csrc/mdk_cohort.hip methyldackel_amd/csrc/mdk_cohort_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_parse_core.h include/mdk_cohort.h
-	@mkdir -p $(B)
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -Imethyldackel_amd/csrc -o $@ methyldackel_amd/csrc/mdk_cohort.hip
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared $(HIPFLAGS) -Iinclude -I$(CSRC) -o $$@ $$<
+endef
+# the tabix index (the first index call)
+$(eval $(call side_lib,index,mdk_tabix.hip,$(CSRC)/mdk_tabix_core.h $(CSRC)/mdk_parse_core.h include/mdk_index.h))
+# the replicates' F test (the first diff_replicates call)
+$(eval $(call side_lib,stats,mdk_qdiff.hip,$(CSRC)/mdk_qdiff_core.h $(CSRC)/mdk_diff_core.h include/mdk_stats.h))
+# the bigWig track (the first render_bigwig / write_bigwig call): mdk_bigwig_core.h's BW_NO_CONTRACT keeps the products unfused, and the file's bytes are the host build's
+$(eval $(call side_lib,track,mdk_bigwig.hip,$(CSRC)/mdk_bigwig_core.h $(CSRC)/mdk_deflate_core.h include/mdk_track.h))
+# smoothing (the first smooth call): mdk_smooth_core.h's MDK_SMO_NO_CONTRACT keeps the products unfused
+$(eval $(call side_lib,smooth,mdk_smooth.hip,$(CSRC)/mdk_smooth_core.h include/mdk_smooth.h))
+# the united table as text and back (the first Cohort.write / render / read call)
+$(eval $(call side_lib,cohort,mdk_cohort.hip,$(CSRC)/mdk_cohort_core.h $(CSRC)/mdk_text_core.h $(CSRC)/mdk_parse_core.h include/mdk_cohort.h))
 
 tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/cohort_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
@@ -106,7 +98,7 @@ tools/_build/smooth_emu: tools/smooth_emu.cpp methyldackel_amd/csrc/mdk_smooth_c
 tools/_build/cohort_emu: tools/cohort_emu.cpp methyldackel_amd/csrc/mdk_cohort_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_parse_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/cohort_emu.cpp -Imethyldackel_amd/csrc
-tools/_build/smooth_bench: tools/smooth_bench.hip methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
+tools/_build/smooth_bench: tools/smooth_bench.hip methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/smooth_bench.hip
 tools/_build/diff_bench: tools/diff_bench.hip methyldackel_amd/csrc/mdk_diff.hip methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_text_internal.hpp methyldackel_amd/csrc/mdk_hip_internal.hpp include/mdk_hip.h

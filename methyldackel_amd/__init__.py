@@ -980,7 +980,7 @@ class _Columns:
         import torch
         L = _text_lib()
         if head:
-            h = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev)
+            h = _device_bytes(head, dev)
             if feed:
                 feed(h)
             yield _deflate(L, self._text, h, False)
@@ -995,11 +995,11 @@ class _Columns:
         blocks = self._text_blocks(fmt, context, block_rows)
         dev = getattr(self, self.COLUMNS[0][0]).device
         if compress:
-            parts = list(self._compressed(blocks, head, dev)) + [torch.frombuffer(bytearray(BGZF_EOF), dtype=torch.uint8).to(dev)]
+            parts = list(self._compressed(blocks, head, dev)) + [_device_bytes(BGZF_EOF, dev)]
             return torch.cat(parts) if len(parts) > 1 else parts[0]
         parts = [b for b in blocks if b.numel()]
         if head:
-            parts.insert(0, torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
+            parts.insert(0, _device_bytes(head, dev))
         return torch.cat(parts) if len(parts) > 1 else parts[0] if parts else torch.empty(0, dtype=torch.uint8, device=dev)
 
     def _write_file(self, path, fmt, context, head, block_rows, compress=False, index=None):
@@ -1010,7 +1010,7 @@ class _Columns:
         import torch
         if index is not None and not compress:
             raise MdkError("index=True needs compress=True: a tabix index is the index of a BGZF file")
-        pin, blocks, ix = None, self._text_blocks(fmt, context, block_rows), None
+        write, blocks, ix = _file_writer(), self._text_blocks(fmt, context, block_rows), None
         try:
             if compress:
                 dev = getattr(self, self.COLUMNS[0][0]).device
@@ -1023,18 +1023,7 @@ class _Columns:
                 f.write(head)
                 at = len(head)
                 for b in blocks:
-                    n = b.numel()
-                    if not n:
-                        continue
-                    if pin is None or pin.numel() < n:
-                        pin = torch.empty(n + n // 8, dtype=torch.uint8, pin_memory=True)
-                    pin[:n].copy_(b, non_blocking=True)
-                    torch.cuda.current_stream(b.device).synchronize()
-                    view = memoryview(pin.numpy())[:n]
-                    if ix:
-                        ix.members_of(view, at)
-                    f.write(view)
-                    at += n
+                    at += write(f, b, (lambda view: ix.members_of(view, at)) if ix else None)        # (the indexer sees a member before it is written)
                 f.write(tail)
             if ix:
                 ix.finish()
@@ -1386,6 +1375,77 @@ def _bgzf_pieces(L, path, buf, members, dev, block_bytes, drop=0, limit=None):
         handle.close()
 
 
+# ---- the side libraries: index, stats, smooth, cohort, track.  Each is one .hip file built into a .so of its own (csrc/mdk_side.hpp is
+# the host layer they share), loaded at the first call that needs it: its code object's load is paid there and by no command ----
+_side_handles = {}                                             # (library, device) -> its md_X handle, opened at the first use and kept
+_side_locks = {name: threading.Lock() for name in ("stats", "smooth", "cohort", "track")}      # a handle's calls come from one thread at a time
+
+
+def _load_side(name, path, noun):
+    """``path`` as a CDLL with what every side library has: md_<name>_last_error, md_<name>_open(device, &handle), md_<name>_close"""
+    if not path.exists():
+        raise MdkError(f"{path} is missing: the {noun} library was not built (run `make` / __graft_entry__.build()); there is no fallback")
+    L = C.CDLL(str(path))
+    getattr(L, f"md_{name}_last_error").restype = C.c_char_p
+    getattr(L, f"md_{name}_open").argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    close = getattr(L, f"md_{name}_close")
+    close.argtypes, close.restype = [C.c_void_p], None
+    return L
+
+
+def _side_call(L, name, f, *args):
+    """md_<name>_<f>(*args); a return code other than 0 raises with the library's text (the caller still holds the handle's lock)"""
+    rc = getattr(L, f"md_{name}_{f}")(*args)
+    if rc:
+        raise _rc_error(f"md_{name}_{f}", rc, getattr(L, f"md_{name}_last_error")().decode())
+
+
+def _side_handle(L, name, device):
+    """the device's md_<name>, opened at its first use and kept; the caller holds ``_side_locks[name]``"""
+    h = _side_handles.get((name, device))
+    if h is None:
+        h = C.c_void_p()
+        _side_call(L, name, "open", device, C.byref(h))
+        _side_handles[name, device] = h
+    return h
+
+
+def _side_limits(L, name, device, *limits):
+    """md_<name>_limits on the device's handle: what ``smooth_limits``, ``cohort_limits`` and ``track_limits`` do"""
+    with _side_locks[name]:
+        _side_call(L, name, "limits", _side_handle(L, name, int(device)), *map(int, limits))
+
+
+def _device_bytes(data, dev):
+    """``data`` (bytes) as a uint8 tensor on ``dev``"""
+    import torch
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+
+
+def _file_writer():
+    """``write(f, t, seen=None)``: the device tensor ``t`` appended to the open file ``f`` through one pinned buffer, kept between the calls
+    and grown by an eighth past the largest tensor: one copy to the host, waited for, then ``seen(bytes)`` if given, then the write.
+    Returns the bytes written"""
+    import torch
+    pin = None
+
+    def write(f, t, seen=None):
+        nonlocal pin
+        k = t.numel()
+        if not k:
+            return 0
+        if pin is None or pin.numel() < k:
+            pin = torch.empty(k + k // 8, dtype=torch.uint8, pin_memory=True)
+        pin[:k].copy_(t, non_blocking=True)
+        torch.cuda.current_stream(t.device).synchronize()
+        view = memoryview(pin.numpy())[:k]
+        if seen:
+            seen(view)
+        f.write(view)
+        return k
+    return write
+
+
 # ---- tabix indexes (include/mdk_index.h, csrc/mdk_tabix.hip -> libmdk_index.so; the rule is csrc/mdk_tabix_core.h) ----
 TABIX_UCSC = 0x10000
 TABIX_PRESETS = {"bed": (TABIX_UCSC, 1, 2, 3, ord("#")), "methylKit": (0, 2, 3, 3, ord("#")), "cytosine_report": (0, 1, 2, 2, ord("#"))}
@@ -1404,17 +1464,13 @@ def lib_index():
     """libmdk_index.so, loaded at the first index call: its code object's load is paid there and by no command"""
     global _index
     if _index is None:
-        if not LIB_INDEX.exists():
-            raise MdkError(f"{LIB_INDEX} is missing: the index library was not built (run `make` / __graft_entry__.build()); there is no fallback")
-        L = C.CDLL(str(LIB_INDEX))
-        L.md_index_last_error.restype = C.c_char_p
+        L = _load_side("index", LIB_INDEX, "index")
         L.md_index_open.argtypes = [C.c_int, C.POINTER(md_index_conf), C.POINTER(C.c_void_p)]
         L.md_index_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.md_index_refusal.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.md_index_finish.argtypes = [C.c_void_p, C.POINTER(md_index_member), C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]
         L.md_index_payload.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.md_index_count.argtypes = [C.c_void_p, C.c_int]; L.md_index_count.restype = C.c_int64
-        L.md_index_close.argtypes = [C.c_void_p]; L.md_index_close.restype = None
         _index = L
     return _index
 
@@ -1482,11 +1538,9 @@ class _TabixIndexer:
         if rc:
             raise _rc_error("md_index_finish", rc, f"{self.path}: {self.L.md_index_last_error().decode()}")
         payload = bytearray(size.value)
-        rc = self.L.md_index_payload(self.h, (C.c_char * size.value).from_buffer(payload), size.value)
-        if rc:
-            raise _rc_error("md_index_payload", rc, self.L.md_index_last_error().decode())
+        _side_call(self.L, "index", "payload", self.h, (C.c_char * size.value).from_buffer(payload), size.value)
         self.counts = {k: int(self.L.md_index_count(self.h, i)) for i, k in enumerate(("lines", "entries", "records", "names", "pieces"))}
-        data = bgzf_compress(torch.frombuffer(payload, dtype=torch.uint8).to(self.dev))
+        data = bgzf_compress(_device_bytes(payload, self.dev))
         with open(self.path + ".tbi", "wb") as f:
             f.write(bytes(data.cpu().numpy()))
         return self.path + ".tbi"
@@ -1851,9 +1905,7 @@ class Calls(_Columns):
         """md_track_bigwig_measure over the columns, under the handle's lock: the file's size"""
         names = (C.c_char_p * len(self.contigs))(*[os.fsencode(s) for s in self.contigs])
         size = C.c_int64()
-        rc = L.md_track_bigwig_measure(h, *[C.c_void_p(t.data_ptr()) for t in cols], int(cols[0].shape[0]), len(self.contigs), names, lengths, value, C.byref(size))
-        if rc:
-            raise _rc_error("md_track_bigwig_measure", rc, L.md_track_last_error().decode())
+        _side_call(L, "track", "bigwig_measure", h, *[C.c_void_p(t.data_ptr()) for t in cols], int(cols[0].shape[0]), len(self.contigs), names, lengths, value, C.byref(size))
         return size.value
 
     def render_bigwig(self, lengths, value="percent", context=None):
@@ -1872,15 +1924,12 @@ class Calls(_Columns):
         cols, lengths, value, dev = self._track_arguments(lengths, value, context)
         L = lib_track()
         torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
-        with _track_lock:                                        # a handle per device, kept: the measured file stays on it until it is filled
-            h = _track_handle(L, dev.index or 0)
+        with _side_locks["track"]:                               # a handle per device, kept: the measured file stays on it until it is filled
+            h = _side_handle(L, "track", dev.index or 0)
             size = self._track_measure(L, h, cols, lengths, value)
             out = torch.empty(size, dtype=torch.uint8, device=dev)
             torch.cuda.current_stream(dev).synchronize()
-            rc = L.md_track_bigwig_fill_range(h, C.c_void_p(out.data_ptr()), 0, size)
-            detail = L.md_track_last_error().decode() if rc else None
-        if rc:
-            raise _rc_error("md_track_bigwig_fill_range", rc, detail)
+            _side_call(L, "track", "bigwig_fill_range", h, C.c_void_p(out.data_ptr()), 0, size)
         return out
 
     def write_bigwig(self, path, lengths, value="percent", context=None, piece_bytes=None):
@@ -1895,21 +1944,17 @@ class Calls(_Columns):
         cols, lengths, value, dev = self._track_arguments(lengths, value, context)
         L = lib_track()
         torch.cuda.current_stream(dev).synchronize()
-        with _track_lock:
-            h = _track_handle(L, dev.index or 0)
+        with _side_locks["track"]:
+            h = _side_handle(L, "track", dev.index or 0)
             size = self._track_measure(L, h, cols, lengths, value)
             piece_bytes = min(piece_bytes, max(size, 1))
-            buf, pin = torch.empty(piece_bytes, dtype=torch.uint8, device=dev), torch.empty(piece_bytes, dtype=torch.uint8, pin_memory=True)
+            buf, write = torch.empty(piece_bytes, dtype=torch.uint8, device=dev), _file_writer()
             torch.cuda.current_stream(dev).synchronize()
             with open(path, "wb") as f:
                 for at in range(0, size, piece_bytes):
                     n = min(piece_bytes, size - at)
-                    rc = L.md_track_bigwig_fill_range(h, C.c_void_p(buf.data_ptr()), at, n)
-                    if rc:
-                        raise _rc_error("md_track_bigwig_fill_range", rc, L.md_track_last_error().decode())
-                    pin[:n].copy_(buf[:n], non_blocking=True)
-                    torch.cuda.current_stream(dev).synchronize()
-                    f.write(memoryview(pin.numpy())[:n])
+                    _side_call(L, "track", "bigwig_fill_range", h, C.c_void_p(buf.data_ptr()), at, n)
+                    write(f, buf[:n])
         return path
 
     @classmethod
@@ -2465,34 +2510,28 @@ class Cohort:
         S, n = self.n_samples, len(self)
         L = lib_cohort()
         torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
-        with _cohort_lock:                                       # a handle per device, kept: its calls come from one thread at a time
+        with _side_locks["cohort"]:                              # a handle per device, kept: its calls come from one thread at a time
             h = _cohort_handle(L, dev.index or 0, self.contigs)
             sites = md_cohort_sites(*[C.c_void_p(getattr(self, name).data_ptr()) for name, _ in SITE_COLUMNS])
             total = C.c_int64()
-            rc = L.md_cohort_measure(h, code, C.byref(sites), C.c_void_p(self.nmeth.data_ptr()), C.c_void_p(self.nunmeth.data_ptr()), S, n, C.byref(total))
-            if rc:
-                raise _rc_error("md_cohort_measure", rc, L.md_cohort_last_error().decode())
+            _side_call(L, "cohort", "measure", h, code, C.byref(sites), C.c_void_p(self.nmeth.data_ptr()), C.c_void_p(self.nunmeth.data_ptr()), S, n, C.byref(total))
             opened()
             emit = (lambda t: sink(bgzf_compress(t, eof=False))) if compress else sink
-            emit(torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev))
+            emit(_device_bytes(head, dev))
             buf, r0 = None, 0
             while r0 < n:
                 r1, size = C.c_int64(), C.c_int64()
-                rc = L.md_cohort_cut(h, r0, piece_bytes, C.byref(r1), C.byref(size))
-                if rc:
-                    raise _rc_error("md_cohort_cut", rc, L.md_cohort_last_error().decode())
+                _side_call(L, "cohort", "cut", h, r0, piece_bytes, C.byref(r1), C.byref(size))
                 if buf is None or buf.numel() < size.value:
                     buf = None
                     buf = torch.empty(max(size.value, min(piece_bytes, total.value)), dtype=torch.uint8, device=dev)
                     torch.cuda.current_stream(dev).synchronize()
-                rc = L.md_cohort_fill(h, r0, r1.value, C.c_void_p(buf.data_ptr()), size.value)
-                if rc:
-                    raise _rc_error("md_cohort_fill", rc, L.md_cohort_last_error().decode())
+                _side_call(L, "cohort", "fill", h, r0, r1.value, C.c_void_p(buf.data_ptr()), size.value)
                 emit(buf[:size.value])
                 torch.cuda.current_stream(dev).synchronize()     # the sink's copies have left the buffer before the next block is made in it
                 r0 = r1.value
             if compress:
-                sink(torch.frombuffer(bytearray(BGZF_EOF), dtype=torch.uint8).to(dev))
+                sink(_device_bytes(BGZF_EOF, dev))
 
     def render(self, fmt="cohort", names=None, compress=False, piece_bytes=None):
         """the bytes ``write`` would put into a file, as a uint8 tensor on the table's device"""
@@ -2515,26 +2554,12 @@ class Cohort:
         plain one.  A negative count, a negative contig or start, a contig index outside ``contigs``, ``end <= start`` and a context
         above 2 raise MdkError (rc -3) naming the first such site (and sample) before the file is opened; so do CPU tensors: there is
         no CPU path.  Rows need not ascend to be written."""
-        import torch
-        state = {"f": None, "pin": None}
-
-        def sink(t):
-            k = t.numel()
-            if not k:
-                return
-            if state["pin"] is None or state["pin"].numel() < k:
-                state["pin"] = torch.empty(k + k // 8, dtype=torch.uint8, pin_memory=True)
-            state["pin"][:k].copy_(t, non_blocking=True)
-            torch.cuda.current_stream(t.device).synchronize()
-            state["f"].write(memoryview(state["pin"].numpy())[:k])
-
-        def opened():
-            state["f"] = open(path, "wb")
+        files, write = [], _file_writer()
         try:
-            self._text_stream(fmt, names, piece_bytes, compress, opened, sink)
+            self._text_stream(fmt, names, piece_bytes, compress, lambda: files.append(open(path, "wb")), lambda t: write(files[0], t))
         finally:
-            if state["f"]:
-                state["f"].close()
+            for f in files:
+                f.close()
         return path
 
     @classmethod
@@ -2584,12 +2609,10 @@ class Cohort:
                 if d.data_ptr() & 15:
                     d = d.clone()
                     torch.cuda.current_stream(dev).synchronize()
-                with _cohort_lock:
+                with _side_locks["cohort"]:
                     h = _cohort_handle(L, dev.index or 0, contigs)
                     rows = C.c_int64()
-                    rc = L.md_cohort_parse_measure(h, C.c_void_p(d.data_ptr()), cut, max(0, hdr - at), S, C.byref(rows))
-                    if rc:
-                        raise _rc_error("md_cohort_parse_measure", rc, L.md_cohort_last_error().decode())
+                    _side_call(L, "cohort", "parse_measure", h, C.c_void_p(d.data_ptr()), cut, max(0, hdr - at), S, C.byref(rows))
                     k = rows.value
                     cols = {name: torch.empty(k, dtype=getattr(torch, dt), device=dev) for name, dt in SITE_COLUMNS}
                     m, u = (torch.empty((S, k), dtype=torch.int32, device=dev) for _ in range(2))
@@ -2686,21 +2709,15 @@ def diff_counts(nmeth, nunmeth, a, b, _text=None):
 
 # ---- the replicates' F test (include/mdk_stats.h, csrc/mdk_qdiff.hip -> libmdk_stats.so; the rule is csrc/mdk_qdiff_core.h) ----
 REPLICATE_RESULT_COLUMNS = DIFF_RESULT_COLUMNS + (("df", "int32"), ("dispersion", "float64"), ("statistic", "float64"))
-_stats, _stats_handles = None, {}
-_stats_lock = threading.Lock()
+_stats = None
 
 
 def lib_stats():
     """libmdk_stats.so, loaded at the first ``diff_replicates`` call: its code object's load is paid there and by no command"""
     global _stats
     if _stats is None:
-        if not LIB_STATS.exists():
-            raise MdkError(f"{LIB_STATS} is missing: the statistics library was not built (run `make` / __graft_entry__.build()); there is no fallback")
-        L = C.CDLL(str(LIB_STATS))
-        L.md_stats_last_error.restype = C.c_char_p
-        L.md_stats_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L = _load_side("stats", LIB_STATS, "statistics")
         L.md_stats_qdiff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 10
-        L.md_stats_close.argtypes = [C.c_void_p]; L.md_stats_close.restype = None
         _stats = L
     return _stats
 
@@ -2734,65 +2751,33 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     if steps:
         out.append(torch.empty(n, dtype=torch.uint32, device=dev))
     torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
-    with _stats_lock:                                        # a handle per device, kept: its calls come from one thread at a time
-        h = _stats_handles.get(dev.index or 0)
-        if h is None:
-            h = C.c_void_p()
-            rc = L.md_stats_open(dev.index or 0, C.byref(h))
-            if rc:
-                raise _rc_error("md_stats_open", rc, L.md_stats_last_error().decode())
-            _stats_handles[dev.index or 0] = h
-        rc = L.md_stats_qdiff(h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(groups[0]), len(groups[1]),
-                              float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
-        detail = L.md_stats_last_error().decode() if rc else None
-    if rc:
-        raise _rc_error("md_stats_qdiff", rc, detail)
+    with _side_locks["stats"]:                               # a handle per device, kept: its calls come from one thread at a time
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "qdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(groups[0]), len(groups[1]),
+                   float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
     return tuple(out)
 
 
 # ---- smoothing (include/mdk_smooth.h, csrc/mdk_smooth.hip -> libmdk_smooth.so; the rule is csrc/mdk_smooth_core.h) ----
 SMOOTH_KERNELS = {"tricube": 0, "flat": 1}                     # SMO_* of csrc/mdk_smooth_core.h
-_smooth, _smooth_handles = None, {}
-_smooth_lock = threading.Lock()
+_smooth = None
 
 
 def lib_smooth():
     """libmdk_smooth.so, loaded at the first ``smooth`` call: its code object's load is paid there and by no command"""
     global _smooth
     if _smooth is None:
-        if not LIB_SMOOTH.exists():
-            raise MdkError(f"{LIB_SMOOTH} is missing: the smoothing library was not built (run `make` / __graft_entry__.build()); there is no fallback")
-        L = C.CDLL(str(LIB_SMOOTH))
-        L.md_smooth_last_error.restype = C.c_char_p
-        L.md_smooth_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L = _load_side("smooth", LIB_SMOOTH, "smoothing")
         L.md_smooth_run.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4
         L.md_smooth_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-        L.md_smooth_close.argtypes = [C.c_void_p]; L.md_smooth_close.restype = None
         _smooth = L
     return _smooth
-
-
-def _smooth_handle(L, device):
-    """the device's md_smooth, opened at its first use and kept; the caller holds ``_smooth_lock``: a handle's calls come from one thread at a time"""
-    h = _smooth_handles.get(device)
-    if h is None:
-        h = C.c_void_p()
-        rc = L.md_smooth_open(device, C.byref(h))
-        if rc:
-            raise _rc_error("md_smooth_open", rc, L.md_smooth_last_error().decode())
-        _smooth_handles[device] = h
-    return h
 
 
 def smooth_limits(device=0, tile_sites=0, chunk_sites=0, sample_batch=0, max_workgroups=0):
     """A test hook (md_smooth_limits): the sites of a workgroup's tile, the rows of a chunk it stages, the samples of a batch and the most
     workgroups of a launch for the smooth calls on ``device`` from now on; 0 is the default of each.  The results do not depend on them."""
-    L = lib_smooth()
-    with _smooth_lock:
-        rc = L.md_smooth_limits(_smooth_handle(L, int(device)), int(tile_sites), int(chunk_sites), int(sample_batch), int(max_workgroups))
-        detail = L.md_smooth_last_error().decode() if rc else None
-    if rc:
-        raise _rc_error("md_smooth_limits", rc, detail)
+    _side_limits(lib_smooth(), "smooth", device, tile_sites, chunk_sites, sample_batch, max_workgroups)
 
 
 def _smooth_arguments(contig, start, nmeth, nunmeth, half_bases, min_sites, kernel):
@@ -2855,13 +2840,10 @@ def smooth_counts(contig, start, nmeth, nunmeth, half_bases=1000, min_sites=70, 
     level, depth = (torch.empty((S, n), dtype=torch.float64, device=dev) for _ in range(2))
     nsites, half = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
     torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
-    with _smooth_lock:                                       # a handle per device, kept: its calls come from one thread at a time
-        h = _smooth_handle(L, dev.index or 0)
-        rc = L.md_smooth_run(h, C.c_void_p(contig.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()),
-                             nmeth.element_size(), S, n, int(half_bases), int(min_sites), code, *[C.c_void_p(t.data_ptr()) for t in (level, depth, nsites, half)])
-        detail = L.md_smooth_last_error().decode() if rc else None
-    if rc:
-        raise _rc_error("md_smooth_run", rc, detail)
+    with _side_locks["smooth"]:                              # a handle per device, kept: its calls come from one thread at a time
+        h = _side_handle(L, "smooth", dev.index or 0)
+        _side_call(L, "smooth", "run", h, C.c_void_p(contig.data_ptr()), C.c_void_p(start.data_ptr()), C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()),
+                   nmeth.element_size(), S, n, int(half_bases), int(min_sites), code, *[C.c_void_p(t.data_ptr()) for t in (level, depth, nsites, half)])
     return level, depth, nsites, half
 
 
@@ -2870,8 +2852,7 @@ COHORT_FORMATS = {"cohort": 0, "methylBase": 1}                # COH_FMT_* of cs
 COHORT_PIECE_BYTES = 64 << 20
 COHORT_SIGNATURE = "#methyldackel_amd cohort 1"
 COHORT_SITE_NAMES = ("#chrom", "start", "end", "context", "strand", "nsamples")
-_cohort, _cohort_handles, _cohort_contigs = None, {}, {}
-_cohort_lock = threading.Lock()
+_cohort, _cohort_contigs = None, {}
 
 
 class md_cohort_sites(C.Structure):
@@ -2882,12 +2863,7 @@ def lib_cohort():
     """libmdk_cohort.so, loaded at the first ``Cohort.write`` / ``render`` / ``read`` call: its code object's load is paid there and by no command"""
     global _cohort
     if _cohort is None:
-        if not LIB_COHORT.exists():
-            raise MdkError(f"{LIB_COHORT} is missing: the cohort text library was not built (run `make` / __graft_entry__.build()); there is no fallback")
-        L = C.CDLL(str(LIB_COHORT))
-        L.md_cohort_last_error.restype = C.c_char_p
-        L.md_cohort_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.md_cohort_close.argtypes = [C.c_void_p]; L.md_cohort_close.restype = None
+        L = _load_side("cohort", LIB_COHORT, "cohort text")
         L.md_cohort_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         L.md_cohort_names.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_int32]
         L.md_cohort_measure.argtypes = [C.c_void_p, C.c_int, C.POINTER(md_cohort_sites), C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
@@ -2902,21 +2878,13 @@ def lib_cohort():
 
 def _cohort_handle(L, device, contigs=None):
     """the device's md_cohort, opened at its first use and kept, with ``contigs`` as its contig names (uploaded when they change); the
-    caller holds ``_cohort_lock``: a handle's calls come from one thread at a time"""
-    h = _cohort_handles.get(device)
-    if h is None:
-        h = C.c_void_p()
-        rc = L.md_cohort_open(device, C.byref(h))
-        if rc:
-            raise _rc_error("md_cohort_open", rc, L.md_cohort_last_error().decode())
-        _cohort_handles[device] = h
+    caller holds ``_side_locks["cohort"]``"""
+    h = _side_handle(L, "cohort", device)
     if contigs is not None and _cohort_contigs.get(device) != tuple(contigs):
         blobs = [str(c).encode() for c in contigs]
         off = (C.c_uint32 * (len(blobs) + 1))(*([0] + list(itertools.accumulate(len(b) for b in blobs))))
         _cohort_contigs.pop(device, None)
-        rc = L.md_cohort_names(h, b"".join(blobs), off, len(blobs))
-        if rc:
-            raise _rc_error("md_cohort_names", rc, L.md_cohort_last_error().decode())
+        _side_call(L, "cohort", "names", h, b"".join(blobs), off, len(blobs))
         _cohort_contigs[device] = tuple(contigs)
     return h
 
@@ -2924,12 +2892,7 @@ def _cohort_handle(L, device, contigs=None):
 def cohort_limits(device=0, tile_sites=0, sample_block=0, max_workgroups=0):
     """A test hook (md_cohort_limits): the sites of a tile, the samples of a block and the most workgroups of a launch for the
     ``Cohort.write`` / ``render`` / ``read`` calls on ``device`` from now on; 0 is the default of each.  No byte and no column depends on them."""
-    L = lib_cohort()
-    with _cohort_lock:
-        rc = L.md_cohort_limits(_cohort_handle(L, int(device)), int(tile_sites), int(sample_block), int(max_workgroups))
-        detail = L.md_cohort_last_error().decode() if rc else None
-    if rc:
-        raise _rc_error("md_cohort_limits", rc, detail)
+    _side_limits(lib_cohort(), "cohort", device, tile_sites, sample_block, max_workgroups)
 
 
 def _cohort_sample_names(names, S):
@@ -3032,20 +2995,14 @@ class Smoothed:
 TRACK_COLUMNS = ("contig", "start", "end", "nmeth", "nunmeth")
 TRACK_VALUES = {"percent": 0, "coverage": 1}                   # BW_VALUE_* of csrc/mdk_bigwig_core.h
 TRACK_PIECE_BYTES = 64 << 20
-_track, _track_handles = None, {}
-_track_lock = threading.Lock()
+_track = None
 
 
 def lib_track():
     """libmdk_track.so, loaded at the first ``render_bigwig`` / ``write_bigwig`` call: its code object's load is paid there and by no command"""
     global _track
     if _track is None:
-        if not LIB_TRACK.exists():
-            raise MdkError(f"{LIB_TRACK} is missing: the track library was not built (run `make` / __graft_entry__.build()); there is no fallback")
-        L = C.CDLL(str(LIB_TRACK))
-        L.md_track_last_error.restype = C.c_char_p
-        L.md_track_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.md_track_close.argtypes = [C.c_void_p]; L.md_track_close.restype = None
+        L = _load_side("track", LIB_TRACK, "track")
         L.md_track_limits.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.md_track_bigwig_measure.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]
         L.md_track_bigwig_fill_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
@@ -3053,27 +3010,10 @@ def lib_track():
     return _track
 
 
-def _track_handle(L, device):
-    """the device's md_track, opened at its first use and kept; the caller holds ``_track_lock``: a handle's calls come from one thread at a time"""
-    h = _track_handles.get(device)
-    if h is None:
-        h = C.c_void_p()
-        rc = L.md_track_open(device, C.byref(h))
-        if rc:
-            raise _rc_error("md_track_open", rc, L.md_track_last_error().decode())
-        _track_handles[device] = h
-    return h
-
-
 def track_limits(device=0, max_workgroups=0, batch_sections=0):
     """A test hook (md_track_limits): at most ``max_workgroups`` workgroups per launch and ``batch_sections`` sections per batch for the
     bigWig calls on ``device`` from now on; 0 is the default of either.  The bytes do not depend on them."""
-    L = lib_track()
-    with _track_lock:
-        rc = L.md_track_limits(_track_handle(L, int(device)), int(max_workgroups), int(batch_sections))
-        detail = L.md_track_last_error().decode() if rc else None
-    if rc:
-        raise _rc_error("md_track_limits", rc, detail)
+    _side_limits(lib_track(), "track", device, max_workgroups, batch_sections)
 
 
 def _benjamini_hochberg(p):

@@ -339,31 +339,19 @@ __global__ __launch_bounds__(BW_WG) void k_bw_pack(const KTrack K) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512];
+#define SIDE_ERR_ARG MD_TRACK_ERR_ARG
+#define SIDE_ERR_HIP MD_TRACK_ERR_HIP
+#define SIDE_ERR_NOMEM MD_TRACK_ERR_NOMEM
+#include "mdk_side.hpp"
 extern "C" const char *md_track_last_error(void) { return g_err; }
-static int fail(int rc, const char *what, hipError_t e) {
-    if(e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); else snprintf(g_err, sizeof g_err, "%s", what);
-    return rc;
-}
-#define TRKCHK(x) do { const hipError_t e_ = (x); if(e_ != hipSuccess) return fail(MD_TRACK_ERR_HIP, #x, e_); } while(0)
 
-// a buffer that is kept and grows with the largest input seen (DeflateState's DflBuf); `pinned`: host memory the device copies to and from
-template <typename T, bool pinned = false> struct TrackBuf {
-    T *p = nullptr; size_t cap = 0;
-    int need(size_t n, const char *what) {
-        if(n <= cap) return 0;
-        release();
-        const size_t want = n + n / 8 + 64;
-        const hipError_t e = pinned ? hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, want * sizeof(T));
-        if(e != hipSuccess) { p = nullptr; return fail(MD_TRACK_ERR_NOMEM, what, e); }
-        cap = want; return 0;
-    }
-    void release() { if(p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+// the handle's buffers grow with the largest input seen: room for what is asked and an eighth more
+template <typename T, bool pinned = false> struct TrackBuf : SideBuf<T, pinned> {
+    int need(size_t n, const char *what) { return SideBuf<T, pinned>::need(n, n + n / 8 + 64, what); }
 };
 
-struct md_track {
-    int device = 0; hipStream_t st = nullptr; int cus = 64, max_wg = 0, batch = BW_BATCH;
-    TrackStatus *d_st = nullptr, *pin = nullptr;
+struct md_track : SideHandle<TrackStatus> {
+    int cus = 64, max_wg = 0, batch = BW_BATCH;
     TrackBuf<uint32_t> meta, chunk, rec, tok, size; TrackBuf<bw_bin> bins; TrackBuf<uint8_t> raw, slots, store, pieces; TrackBuf<long long> off; TrackBuf<bw_entry> entry;
     TrackBuf<uint32_t, true> h_meta, h_size; TrackBuf<bw_bin, true> h_top; TrackBuf<bw_entry, true> h_entry; TrackBuf<uint8_t, true> h_pieces;
     // the measured file
@@ -371,29 +359,17 @@ struct md_track {
 };
 
 extern "C" int md_track_open(int device, md_track **out) {
-    if(!out) return fail(MD_TRACK_ERR_ARG, "md_track_open", hipSuccess);
-    *out = nullptr;
-    TRKCHK(hipSetDevice(device));
-    md_track *h = new md_track();
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
-    if(e == hipSuccess) e = hipMalloc((void **)&h->d_st, sizeof(TrackStatus));
-    if(e == hipSuccess) e = hipHostMalloc((void **)&h->pin, sizeof(TrackStatus), hipHostMallocDefault);
-    if(e != hipSuccess) { md_track_close(h); return fail(MD_TRACK_ERR_NOMEM, "md_track_open", e); }
-    if(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cus < 1) h->cus = 64;
-    *out = h;
-    return 0;
+    return side_open(device, out, "md_track_open", md_track_close, [](md_track *h) {
+        if(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->cus < 1) h->cus = 64;
+        return hipSuccess; });
 }
 
 extern "C" void md_track_close(md_track *h) {
     if(!h) return;
-    (void)hipSetDevice(h->device);
-    if(h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
+    h->close();
     h->meta.release(); h->chunk.release(); h->rec.release(); h->tok.release(); h->size.release(); h->bins.release(); h->raw.release(); h->slots.release();
     h->store.release(); h->pieces.release(); h->off.release(); h->entry.release();
     h->h_meta.release(); h->h_size.release(); h->h_top.release(); h->h_entry.release(); h->h_pieces.release();
-    (void)hipFree(h->d_st);
-    if(h->pin) (void)hipHostFree(h->pin);
     delete h;
 }
 
@@ -418,8 +394,8 @@ static int upload_pieces(md_track *h, const char *what) {
     int rc;
     if((rc = h->h_pieces.need(bytes, what)) || (rc = h->pieces.need(bytes, what))) return rc;
     for(size_t i = 0; i < h->lay.pieces.size(); i++) memcpy(h->h_pieces.p + h->piece_at[i], h->lay.pieces[i].bytes.data(), h->lay.pieces[i].bytes.size());
-    TRKCHK(hipMemcpyAsync(h->pieces.p, h->h_pieces.p, bytes, hipMemcpyHostToDevice, h->st));
-    TRKCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipMemcpyAsync(h->pieces.p, h->h_pieces.p, bytes, hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     return 0;
 }
 
@@ -440,7 +416,7 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
         }
         name[c] = names[c]; len[c] = (uint32_t)lengths[c];
     }
-    TRKCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     bool written[BW_LEVELS]; int64_t zcount[BW_LEVELS]; uint64_t zsec[BW_LEVELS];
     for(int k = 0; k < BW_LEVELS; k++) { written[k] = false; zcount[k] = 0; zsec[k] = 0; }
     bw_summary total = {0, 0.0, 0.0, 0.0, 0.0};
@@ -481,15 +457,14 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
         }
     }
     memset(h->pin, 0, sizeof(TrackStatus));
-    h->pin->first = ~0ull;
-    TRKCHK(hipMemcpyAsync(h->meta.p, hm, meta_n * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
-    TRKCHK(hipMemcpyAsync(h->d_st, h->pin, sizeof(TrackStatus), hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipMemcpyAsync(h->meta.p, hm, meta_n * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+    SIDE_STATUS_UP(h, h->pin, TrackStatus);
     // ---- the rows ----
     hipLaunchKernelGGL(k_bw_check, dim3(grid_of(h, ((uint64_t)n + BW_WG - 1) / BW_WG, 32)), dim3(BW_WG), 0, h->st, K);
-    TRKCHK(hipGetLastError());
-    TRKCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(TrackStatus), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipMemcpyAsync(hm + o_first, h->meta.p + o_first, 2 * (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDECHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(TrackStatus), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipMemcpyAsync(hm + o_first, h->meta.p + o_first, 2 * (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     if(h->pin->first != ~0ull) {
         snprintf(g_err, sizeof g_err, "row %llu: %s", h->pin->first >> 8, bw_error_text((uint32_t)(h->pin->first & 0xffu)));
         return MD_TRACK_ERR_ARG;
@@ -504,18 +479,18 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
     }
     hm[o_sec + nc] = (uint32_t)n_data;
     K.n_data = (uint32_t)n_data;
-    TRKCHK(hipMemcpyAsync(h->meta.p + o_sec, hm + o_sec, ((size_t)nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipMemcpyAsync(h->meta.p + o_sec, hm + o_sec, ((size_t)nc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->st));
     // ---- zoom: all eight levels, their counts ----
     hipLaunchKernelGGL(k_bw_zoom0, dim3(grid_of(h, (bins_n[0] + BW_WG - 1) / BW_WG, 32)), dim3(BW_WG), 0, h->st, K);
     for(int k = 1; k < BW_LEVELS; k++) { K.level = k; hipLaunchKernelGGL(k_bw_zoomk, dim3(grid_of(h, (bins_n[k] + BW_WG - 1) / BW_WG, 32)), dim3(BW_WG), 0, h->st, K); }
     for(int k = 0; k < BW_LEVELS; k++) { K.level = k; hipLaunchKernelGGL(k_bw_count, dim3(grid_of(h, chunks_n[k], 32)), dim3(BW_WG), 0, h->st, K); }
     hipLaunchKernelGGL(k_bw_scan, dim3(BW_LEVELS), dim3(BW_WG), 0, h->st, K);
-    TRKCHK(hipGetLastError());
+    SIDECHK(hipGetLastError());
     const size_t top_n = (size_t)bins_n[BW_LEVELS - 1];
     if((rc = h->h_top.need(top_n, what))) return rc;
-    TRKCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(TrackStatus), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipMemcpyAsync(h->h_top.p, K.bins[BW_LEVELS - 1], top_n * sizeof(bw_bin), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(TrackStatus), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipMemcpyAsync(h->h_top.p, K.bins[BW_LEVELS - 1], top_n * sizeof(bw_bin), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     for(int k = 0; k < BW_LEVELS; k++) zcount[k] = h->pin->zcount[k];
     bw_plan_levels(n, zcount, written);
     for(size_t x = 0; x < top_n; x++) bw_total_add(total, h->h_top.p[x]);
@@ -535,7 +510,7 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
     if((rc = h->rec.need((size_t)rec_all * 8, what))) return rc;
     K.rec = h->rec.p;
     for(int k = 0; k < BW_LEVELS; k++) if(written[k]) { K.level = k; hipLaunchKernelGGL(k_bw_records, dim3(grid_of(h, chunks_n[k], 32)), dim3(BW_WG), 0, h->st, K); }
-    TRKCHK(hipGetLastError());
+    SIDECHK(hipGetLastError());
     // ---- the sections, a batch at a time ----
     const uint32_t batch = (uint32_t)h->batch, zgrid = grid_of(h, batch, 5);          // dfl_state is ~29 KiB of LDS: five wavefronts a compute unit
     if((rc = h->size.need((size_t)n_sec, what)) || (rc = h->entry.need((size_t)n_sec, what)) || (rc = h->h_size.need((size_t)n_sec, what)) || (rc = h->h_entry.need((size_t)n_sec, what)) ||
@@ -550,9 +525,8 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
         const uint32_t g = grid_of(h, b1 - b0, 5);
         hipLaunchKernelGGL(k_bw_zlib, dim3(g < zgrid ? g : zgrid), dim3(64), 0, h->st, K);
         hipLaunchKernelGGL(k_bw_offsets, dim3(1), dim3(BW_WG), 0, h->st, K);
-        TRKCHK(hipGetLastError());
-        TRKCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(TrackStatus), hipMemcpyDeviceToHost, h->st));
-        TRKCHK(hipStreamSynchronize(h->st));
+        SIDECHK(hipGetLastError());
+        SIDE_STATUS_DOWN(h, h->pin, TrackStatus);
         if(h->pin->err) { snprintf(g_err, sizeof g_err, "%s: a section does not fit its slot, or a level's records are not the counted ones", what); return MD_TRACK_ERR_HIP; }
         const long long need = store_at + h->pin->batch_bytes;
         if((size_t)need > h->store.cap) {                          // the store grows and keeps what the batches before left in it
@@ -566,12 +540,12 @@ extern "C" int md_track_bigwig_measure(md_track *h, const int32_t *contig, const
         }
         K.store = h->store.p;
         hipLaunchKernelGGL(k_bw_pack, dim3(grid_of(h, b1 - b0, 32)), dim3(BW_WG), 0, h->st, K);
-        TRKCHK(hipGetLastError());
+        SIDECHK(hipGetLastError());
         store_at = need;
     }
-    TRKCHK(hipMemcpyAsync(h->h_size.p, h->size.p, (size_t)n_sec * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipMemcpyAsync(h->h_entry.p, h->entry.p, (size_t)n_sec * sizeof(bw_entry), hipMemcpyDeviceToHost, h->st));
-    TRKCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipMemcpyAsync(h->h_size.p, h->size.p, (size_t)n_sec * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipMemcpyAsync(h->h_entry.p, h->entry.p, (size_t)n_sec * sizeof(bw_entry), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     // ---- the file ----
     h->lay = bw_make_layout(name, len, n_data, written, zcount, zsec, h->h_entry.p, h->h_size.p, raw_max, total);
     h->regions = bw_make_regions(h->lay, n_data, written, zsec, h->h_size.p);
@@ -585,14 +559,14 @@ extern "C" int md_track_bigwig_fill_range(md_track *h, void *d_out, int64_t offs
     if(!h || !h->measured) return fail(MD_TRACK_ERR_ARG, "md_track_bigwig_fill_range: md_track_bigwig_measure first", hipSuccess);
     if(offset < 0 || bytes < 0 || offset > h->lay.total || bytes > h->lay.total - offset || (bytes && !d_out)) return fail(MD_TRACK_ERR_ARG, "md_track_bigwig_fill_range: the range must lie inside the measured file", hipSuccess);
     if(!bytes) return 0;
-    TRKCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     int64_t got = 0;
     for(const bw_cut &c : bw_cut_range(h->lay, h->regions, offset, bytes)) {
         const uint8_t *const src = c.piece ? h->pieces.p + h->piece_at[c.index] + c.src : h->store.p + c.src;
-        TRKCHK(hipMemcpyAsync((uint8_t *)d_out + c.dst, src, (size_t)c.bytes, hipMemcpyDeviceToDevice, h->st));
+        SIDECHK(hipMemcpyAsync((uint8_t *)d_out + c.dst, src, (size_t)c.bytes, hipMemcpyDeviceToDevice, h->st));
         got += c.bytes;
     }
-    TRKCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     if(got != bytes) return fail(MD_TRACK_ERR_HIP, "md_track_bigwig_fill_range: the layout's pieces and regions do not cover the range", hipSuccess);
     return 0;
 }

@@ -317,55 +317,31 @@ __global__ __launch_bounds__(COH_WG) void k_cparse_order(const KCohR K) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512];
+#define SIDE_ERR_ARG MD_COHORT_ERR_ARG
+#define SIDE_ERR_HIP MD_COHORT_ERR_HIP
+#define SIDE_ERR_NOMEM MD_COHORT_ERR_NOMEM
+#include "mdk_side.hpp"
 extern "C" const char *md_cohort_last_error(void) { return g_err; }
-static int fail(int rc, const char *what, hipError_t e) {
-    if(e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); else snprintf(g_err, sizeof g_err, "%s", what);
-    return rc;
-}
-#define COHCHK(x) do { const hipError_t e_ = (x); if(e_ != hipSuccess) return fail(MD_COHORT_ERR_HIP, #x, e_); } while(0)
 
-struct md_cohort {
-    int device = 0; hipStream_t st = nullptr;
-    CohStatus *d_st = nullptr, *pin = nullptr; int64_t *pin64 = nullptr;
+struct md_cohort : SideHandle<CohStatus> {
+    int64_t *pin64 = nullptr;
     int32_t tile = COH_TILE_DEFAULT, sblock = COH_BLOCK_DEFAULT, grid = COH_GRID_DEFAULT;
     uint32_t *d_name_off = nullptr, *d_sorted = nullptr; uint8_t *d_names = nullptr; int32_t n_contigs = 0;
-    int64_t *d_len = nullptr; int64_t len_cap = 0; uint16_t *d_part = nullptr; int64_t part_cap = 0;
+    SideBuf<int64_t> d_len; SideBuf<uint16_t> d_part;          // (these four: as large as the largest table asked for, and no larger)
     KCohW W; bool measured = false; int64_t total = 0;
-    int64_t *d_cnt = nullptr; int64_t cnt_cap = 0; int64_t *d_line = nullptr; int64_t line_cap = 0;
+    SideBuf<int64_t> d_cnt, d_line;
     KCohR P; bool counted = false; int64_t err_offset = -1;
 };
 
-template <typename T> static hipError_t coh_grow(T **p, int64_t *cap, int64_t need) {
-    if(need <= *cap) return hipSuccess;
-    (void)hipFree(*p); *p = nullptr; *cap = 0;
-    const hipError_t e = hipMalloc((void **)p, (size_t)need * sizeof(T));
-    if(e == hipSuccess) *cap = need;
-    return e;
-}
-
 extern "C" int md_cohort_open(int device, md_cohort **out) {
-    if(!out) return fail(MD_COHORT_ERR_ARG, "md_cohort_open", hipSuccess);
-    *out = nullptr;
-    COHCHK(hipSetDevice(device));
-    md_cohort *h = new md_cohort();
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
-    if(e == hipSuccess) e = hipMalloc((void **)&h->d_st, sizeof(CohStatus));
-    if(e == hipSuccess) e = hipHostMalloc((void **)&h->pin, sizeof(CohStatus), hipHostMallocDefault);
-    if(e == hipSuccess) e = hipHostMalloc((void **)&h->pin64, 2 * sizeof(int64_t), hipHostMallocDefault);
-    if(e != hipSuccess) { md_cohort_close(h); return fail(MD_COHORT_ERR_NOMEM, "md_cohort_open", e); }
-    *out = h;
-    return 0;
+    return side_open(device, out, "md_cohort_open", md_cohort_close, [](md_cohort *h) { return hipHostMalloc((void **)&h->pin64, 2 * sizeof(int64_t), hipHostMallocDefault); });
 }
 
 extern "C" void md_cohort_close(md_cohort *h) {
     if(!h) return;
-    (void)hipSetDevice(h->device);
-    if(h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    (void)hipFree(h->d_st); (void)hipFree(h->d_name_off); (void)hipFree(h->d_sorted); (void)hipFree(h->d_names);
-    (void)hipFree(h->d_len); (void)hipFree(h->d_part); (void)hipFree(h->d_cnt); (void)hipFree(h->d_line);
-    if(h->pin) (void)hipHostFree(h->pin);
+    h->close();
+    (void)hipFree(h->d_name_off); (void)hipFree(h->d_sorted); (void)hipFree(h->d_names);
+    h->d_len.release(); h->d_part.release(); h->d_cnt.release(); h->d_line.release();
     if(h->pin64) (void)hipHostFree(h->pin64);
     delete h;
 }
@@ -396,7 +372,7 @@ extern "C" int md_cohort_names(md_cohort *h, const uint8_t *names, const uint32_
             snprintf(g_err, sizeof g_err, "%s: contig %d's name is empty or longer than %d bytes", what, c, MD_TEXT_NAME_MAX);
             return MD_COHORT_ERR_ARG;
         }
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     (void)hipFree(h->d_name_off); (void)hipFree(h->d_sorted); (void)hipFree(h->d_names);
     h->d_name_off = h->d_sorted = nullptr; h->d_names = nullptr; h->n_contigs = 0; h->measured = false; h->counted = false;
     const uint32_t zero = 0, total = n_contigs ? name_off[n_contigs] : 0;
@@ -404,19 +380,13 @@ extern "C" int md_cohort_names(md_cohort *h, const uint8_t *names, const uint32_
     for(int32_t c = 0; c < n_contigs; c++) sorted[c] = (uint32_t)c;
     std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
         return prs_name_cmp(names + name_off[a], name_off[a + 1] - name_off[a], names + name_off[b], name_off[b + 1] - name_off[b]) < 0; });
-    COHCHK(hipMalloc((void **)&h->d_name_off, (size_t)(n_contigs + 1) * sizeof(uint32_t)));
-    COHCHK(hipMalloc((void **)&h->d_sorted, (size_t)(n_contigs + 1) * sizeof(uint32_t)));
-    COHCHK(hipMalloc((void **)&h->d_names, (size_t)total + 16));
-    COHCHK(hipMemcpy(h->d_name_off, n_contigs ? name_off : &zero, (size_t)(n_contigs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if(n_contigs) COHCHK(hipMemcpy(h->d_sorted, sorted.data(), (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if(total) COHCHK(hipMemcpy(h->d_names, names, total, hipMemcpyHostToDevice));
+    SIDECHK(hipMalloc((void **)&h->d_name_off, (size_t)(n_contigs + 1) * sizeof(uint32_t)));
+    SIDECHK(hipMalloc((void **)&h->d_sorted, (size_t)(n_contigs + 1) * sizeof(uint32_t)));
+    SIDECHK(hipMalloc((void **)&h->d_names, (size_t)total + 16));
+    SIDECHK(hipMemcpy(h->d_name_off, n_contigs ? name_off : &zero, (size_t)(n_contigs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if(n_contigs) SIDECHK(hipMemcpy(h->d_sorted, sorted.data(), (size_t)n_contigs * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if(total) SIDECHK(hipMemcpy(h->d_names, names, total, hipMemcpyHostToDevice));
     h->n_contigs = n_contigs;
-    return 0;
-}
-
-static int coh_status_reset(md_cohort *h) {
-    h->pin->first = ~0ull;
-    COHCHK(hipMemcpyAsync(h->d_st, h->pin, sizeof(CohStatus), hipMemcpyHostToDevice, h->st));
     return 0;
 }
 
@@ -426,27 +396,27 @@ extern "C" int md_cohort_measure(md_cohort *h, int fmt, const md_cohort_sites *s
     if(n && (!sites || !sites->contig || !sites->start || !sites->end || !sites->context || !sites->strand || !sites->nsamples || !nmeth || !nunmeth)) return fail(MD_COHORT_ERR_ARG, what, hipSuccess);
     if(!h->d_name_off) return fail(MD_COHORT_ERR_ARG, "md_cohort_measure: no contig names (md_cohort_names)", hipSuccess);
     h->measured = false; *total_bytes = 0;
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     KCohW &K = h->W;
     K.S = n_samples; K.n = n; K.fmt = fmt; K.tile = h->tile; K.sblock = n_samples < h->sblock ? n_samples : h->sblock; K.nb = (n_samples + K.sblock - 1) / K.sblock;
-    if(coh_grow(&h->d_len, &h->len_cap, n + 1) != hipSuccess || coh_grow(&h->d_part, &h->part_cap, (n ? n : 1) * K.nb) != hipSuccess)
-        return fail(MD_COHORT_ERR_NOMEM, "md_cohort_measure: the lines' lengths", hipErrorOutOfMemory);
+    if(int rc = h->d_len.need((size_t)n + 1, "md_cohort_measure: the lines' lengths")) return rc;
+    if(int rc = h->d_part.need((size_t)(n ? n : 1) * K.nb, "md_cohort_measure: the lines' lengths")) return rc;
     if(n) {
         K.contig = (const int32_t *)sites->contig; K.start = (const int32_t *)sites->start; K.end = (const int32_t *)sites->end;
         K.context = (const uint8_t *)sites->context; K.strand = (const int8_t *)sites->strand; K.nsamples = (const int32_t *)sites->nsamples;
     }
     K.m = nmeth; K.u = nunmeth; K.name_off = h->d_name_off; K.names = h->d_names; K.n_contigs = h->n_contigs;
     K.len = h->d_len; K.part = h->d_part; K.st = h->d_st; K.r0 = K.r1 = K.base = 0; K.out = nullptr;
-    if(int rc = coh_status_reset(h)) return rc;
+    SIDE_STATUS_UP(h, h->pin, CohStatus);
     if(n) {
         hipLaunchKernelGGL(k_ctext_len, dim3((uint32_t)((n + COH_WG - 1) / COH_WG)), dim3(COH_WG), 0, h->st, K);
-        COHCHK(hipGetLastError());
+        SIDECHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_scan64, dim3(1), dim3(1024), 0, h->st, h->d_len, n);
-    COHCHK(hipGetLastError());
-    COHCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(CohStatus), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipMemcpyAsync(h->pin64, h->d_len + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDECHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(CohStatus), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipMemcpyAsync(h->pin64, h->d_len + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     const unsigned long long first = h->pin->first;
     if(first != ~0ull) {
         const uint32_t w = (uint32_t)(first >> 11) & 31u;
@@ -459,15 +429,15 @@ extern "C" int md_cohort_measure(md_cohort *h, int fmt, const md_cohort_sites *s
 }
 
 static int coh_offset(md_cohort *h, int64_t row, int64_t *v) {
-    COHCHK(hipMemcpyAsync(h->pin64, h->d_len + row, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipMemcpyAsync(h->pin64, h->d_len + row, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     *v = h->pin64[0];
     return 0;
 }
 
 extern "C" int md_cohort_cut(md_cohort *h, int64_t row0, int64_t max_bytes, int64_t *row1, int64_t *bytes) {
     if(!h || !h->measured || !row1 || !bytes || row0 < 0 || row0 >= h->W.n || max_bytes < 1) return fail(MD_COHORT_ERR_ARG, "md_cohort_cut", hipSuccess);
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     int64_t base, v;
     if(int rc = coh_offset(h, row0, &base)) return rc;
     int64_t lo = row0 + 1, hi = h->W.n;                                     // the largest r in [row0 + 1, n] with offset[r] - base <= max_bytes, or row0 + 1
@@ -484,7 +454,7 @@ extern "C" int md_cohort_cut(md_cohort *h, int64_t row0, int64_t max_bytes, int6
 extern "C" int md_cohort_fill(md_cohort *h, int64_t row0, int64_t row1, void *out, int64_t bytes) {
     const char *const what = "md_cohort_fill";
     if(!h || !h->measured || row0 < 0 || row1 <= row0 || row1 > h->W.n || !out) return fail(MD_COHORT_ERR_ARG, what, hipSuccess);
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     int64_t base, end;
     if(int rc = coh_offset(h, row0, &base)) return rc;
     if(int rc = coh_offset(h, row1, &end)) return rc;
@@ -493,8 +463,8 @@ extern "C" int md_cohort_fill(md_cohort *h, int64_t row0, int64_t row1, void *ou
     K.r0 = row0; K.r1 = row1; K.base = base; K.out = (uint8_t *)out;
     const int64_t items = ((row1 - row0 + K.tile - 1) / K.tile) * (K.nb + 1);
     hipLaunchKernelGGL(k_ctext_fill, dim3((uint32_t)(items < h->grid ? items : h->grid)), dim3(COH_WG), coh_fill_lds(K.tile, K.sblock), h->st, K);
-    COHCHK(hipGetLastError());
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDECHK(hipStreamSynchronize(h->st));
     return 0;
 }
 
@@ -504,28 +474,28 @@ extern "C" int md_cohort_parse_measure(md_cohort *h, const void *text, int64_t b
         return fail(MD_COHORT_ERR_ARG, what, hipSuccess);
     if(!h->d_name_off) return fail(MD_COHORT_ERR_ARG, "md_cohort_parse_measure: no contig names (md_cohort_names)", hipSuccess);
     h->counted = false; h->err_offset = -1; *rows = 0;
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     KCohR &K = h->P;
     memset(&K, 0, sizeof K);
     const int64_t spans = (bytes + COH_SPAN - 1) / COH_SPAN;
-    if(coh_grow(&h->d_cnt, &h->cnt_cap, spans + 1) != hipSuccess) return fail(MD_COHORT_ERR_NOMEM, "md_cohort_parse_measure: the spans' counts", hipErrorOutOfMemory);
+    if(int rc = h->d_cnt.need((size_t)spans + 1, "md_cohort_parse_measure: the spans' counts")) return rc;
     K.text = (const uint8_t *)text; K.bytes = bytes; K.begin = begin; K.S = n_samples;
     K.name_off = h->d_name_off; K.names = h->d_names; K.sorted = h->d_sorted; K.n_contigs = h->n_contigs; K.cnt = h->d_cnt; K.st = h->d_st;
     if(spans) {
         hipLaunchKernelGGL(k_cparse_len, dim3((uint32_t)spans), dim3(COH_WG), 0, h->st, K);
-        COHCHK(hipGetLastError());
+        SIDECHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_scan64, dim3(1), dim3(1024), 0, h->st, h->d_cnt, spans);
-    COHCHK(hipGetLastError());
-    COHCHK(hipMemcpyAsync(h->pin64, h->d_cnt + spans, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDECHK(hipMemcpyAsync(h->pin64, h->d_cnt + spans, sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     K.rows = *rows = h->pin64[0];
-    if(coh_grow(&h->d_line, &h->line_cap, K.rows + 1) != hipSuccess) return fail(MD_COHORT_ERR_NOMEM, "md_cohort_parse_measure: the line starts", hipErrorOutOfMemory);
+    if(int rc = h->d_line.need((size_t)K.rows + 1, "md_cohort_parse_measure: the line starts")) return rc;
     K.line = h->d_line;
     if(K.rows) {
         hipLaunchKernelGGL(k_cparse_starts, dim3((uint32_t)spans), dim3(COH_WG), 0, h->st, K);
-        COHCHK(hipGetLastError());
-        COHCHK(hipStreamSynchronize(h->st));
+        SIDECHK(hipGetLastError());
+        SIDECHK(hipStreamSynchronize(h->st));
     }
     h->counted = true;
     return 0;
@@ -538,7 +508,7 @@ extern "C" int md_cohort_parse_fill(md_cohort *h, const md_cohort_sites *sites, 
     h->counted = false;
     if(!rows) return 0;
     if(!sites || !sites->contig || !sites->start || !sites->end || !sites->context || !sites->strand || !sites->nsamples || !nmeth || !nunmeth) return fail(MD_COHORT_ERR_ARG, what, hipSuccess);
-    COHCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     KCohR K = h->P;
     // the sites' columns hold THIS text's rows from their entry 0; the matrices hold them from row_at
     K.contig = (int32_t *)sites->contig; K.start = (int32_t *)sites->start; K.end = (int32_t *)sites->end;
@@ -550,18 +520,17 @@ extern "C" int md_cohort_parse_fill(md_cohort *h, const md_cohort_sites *sites, 
     auto lds = [&](int32_t r) { return (size_t)8 * K.S * (r | 1) + (size_t)r * (COH_SITE_FIELDS + 1) * 4; };
     while(R > 1 && lds(R) > COH_LDS_BYTES) R--;
     K.R = R; K.Rp = R | 1;
-    if(int rc = coh_status_reset(h)) return rc;
+    SIDE_STATUS_UP(h, h->pin, CohStatus);
     const int64_t ntiles = (rows + R - 1) / R;
     hipLaunchKernelGGL(k_cparse_fill, dim3((uint32_t)(ntiles < h->grid ? ntiles : h->grid)), dim3(COH_WG), lds(R), h->st, K);
-    COHCHK(hipGetLastError());
+    SIDECHK(hipGetLastError());
     hipLaunchKernelGGL(k_cparse_order, dim3((uint32_t)((rows + COH_WG - 1) / COH_WG)), dim3(COH_WG), 0, h->st, K);
-    COHCHK(hipGetLastError());
-    COHCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(CohStatus), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDE_STATUS_DOWN(h, h->pin, CohStatus);
     const unsigned long long first = h->pin->first;
     if(first == ~0ull) return 0;
-    COHCHK(hipMemcpyAsync(h->pin64, h->d_line + (int64_t)(first >> 8), sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
-    COHCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipMemcpyAsync(h->pin64, h->d_line + (int64_t)(first >> 8), sizeof(int64_t), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     h->err_offset = h->pin64[0];
     snprintf(g_err, sizeof g_err, "%s", coh_error_text((uint32_t)(first & 0xffu)));
     return MD_COHORT_ERR_ARG;

@@ -83,41 +83,23 @@ __global__ __launch_bounds__(QDIFF_WG) void k_qdiff(const KQdiff K) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512];
+#define SIDE_ERR_ARG MD_STATS_ERR_ARG
+#define SIDE_ERR_HIP MD_STATS_ERR_HIP
+#define SIDE_ERR_NOMEM MD_STATS_ERR_NOMEM
+#include "mdk_side.hpp"
 extern "C" const char *md_stats_last_error(void) { return g_err; }
-static int fail(int rc, const char *what, hipError_t e) {
-    if(e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); else snprintf(g_err, sizeof g_err, "%s", what);
-    return rc;
-}
-#define STATCHK(x) do { const hipError_t e_ = (x); if(e_ != hipSuccess) return fail(MD_STATS_ERR_HIP, #x, e_); } while(0)
 
-struct md_stats {
-    int device = 0; hipStream_t st = nullptr;
-    StatsStatus *d_st = nullptr; int32_t *d_order = nullptr;
-    StatsPinned *pin = nullptr;
+struct md_stats : SideHandle<StatsStatus, StatsPinned> {
+    int32_t *d_order = nullptr;
 };
 
 extern "C" int md_stats_open(int device, md_stats **out) {
-    if(!out) return fail(MD_STATS_ERR_ARG, "md_stats_open", hipSuccess);
-    *out = nullptr;
-    STATCHK(hipSetDevice(device));
-    md_stats *h = new md_stats();
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
-    if(e == hipSuccess) e = hipMalloc((void **)&h->d_st, sizeof(StatsStatus));
-    if(e == hipSuccess) e = hipMalloc((void **)&h->d_order, DIFF_MAX_SAMPLES * sizeof(int32_t));
-    if(e == hipSuccess) e = hipHostMalloc((void **)&h->pin, sizeof(StatsPinned), hipHostMallocDefault);
-    if(e != hipSuccess) { md_stats_close(h); return fail(MD_STATS_ERR_NOMEM, "md_stats_open", e); }
-    *out = h;
-    return 0;
+    return side_open(device, out, "md_stats_open", md_stats_close, [](md_stats *h) { return hipMalloc((void **)&h->d_order, DIFF_MAX_SAMPLES * sizeof(int32_t)); });
 }
 
 extern "C" void md_stats_close(md_stats *h) {
     if(!h) return;
-    (void)hipSetDevice(h->device);
-    if(h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    (void)hipFree(h->d_st); (void)hipFree(h->d_order);
-    if(h->pin) (void)hipHostFree(h->pin);
+    h->close(); (void)hipFree(h->d_order);
     delete h;
 }
 
@@ -158,11 +140,10 @@ extern "C" int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmet
         seen[s] = true;
     }
     if(!n) return 0;
-    STATCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     memcpy(h->pin->order, order, (size_t)(n_a + n_b) * sizeof(int32_t));
-    h->pin->st.first = ~0ull;
-    STATCHK(hipMemcpyAsync(h->d_order, h->pin->order, (size_t)(n_a + n_b) * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    STATCHK(hipMemcpyAsync(h->d_st, &h->pin->st, sizeof(StatsStatus), hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipMemcpyAsync(h->d_order, h->pin->order, (size_t)(n_a + n_b) * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    SIDE_STATUS_UP(h, &h->pin->st, StatsStatus);
     KQdiff K;
     K.m = nmeth; K.u = nunmeth; K.order = h->d_order; K.n_a = n_a; K.n_b = n_b; K.n = n; K.min_dispersion = min_dispersion;
     K.a = nmeth_a; K.b = nunmeth_a; K.c = nmeth_b; K.d = nunmeth_b; K.diff = meth_diff; K.p = pvalue; K.df = df; K.dispersion = dispersion; K.statistic = statistic;
@@ -170,9 +151,8 @@ extern "C" int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmet
     const dim3 grid((uint32_t)((n + QDIFF_WG - 1) / QDIFF_WG));
     if(elem_bytes == 4) hipLaunchKernelGGL(k_qdiff<int32_t>, grid, dim3(QDIFF_WG), 0, h->st, K);
     else hipLaunchKernelGGL(k_qdiff<int64_t>, grid, dim3(QDIFF_WG), 0, h->st, K);
-    STATCHK(hipGetLastError());
-    STATCHK(hipMemcpyAsync(&h->pin->st, h->d_st, sizeof(StatsStatus), hipMemcpyDeviceToHost, h->st));
-    STATCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDE_STATUS_DOWN(h, &h->pin->st, StatsStatus);
     const unsigned long long first = h->pin->st.first;
     if(first == ~0ull) return 0;
     const uint32_t bit = 1u << (first & 0xffu);

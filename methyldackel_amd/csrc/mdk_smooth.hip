@@ -136,43 +136,24 @@ __global__ __launch_bounds__(SMO_WG) void k_smooth_sum(const KSmooth K) {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512];
+#define SIDE_ERR_ARG MD_SMOOTH_ERR_ARG
+#define SIDE_ERR_HIP MD_SMOOTH_ERR_HIP
+#define SIDE_ERR_NOMEM MD_SMOOTH_ERR_NOMEM
+#include "mdk_side.hpp"
 extern "C" const char *md_smooth_last_error(void) { return g_err; }
-static int fail(int rc, const char *what, hipError_t e) {
-    if(e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); else snprintf(g_err, sizeof g_err, "%s", what);
-    return rc;
-}
-#define SMOCHK(x) do { const hipError_t e_ = (x); if(e_ != hipSuccess) return fail(MD_SMOOTH_ERR_HIP, #x, e_); } while(0)
 
-struct md_smooth {
-    int device = 0; hipStream_t st = nullptr;
-    SmoothStatus *d_st = nullptr, *pin = nullptr;
-    int32_t *d_lo = nullptr; int64_t lo_cap = 0;               // lo of every site: the window kernel's word to the sum kernel
+struct md_smooth : SideHandle<SmoothStatus> {
+    SideBuf<int32_t> d_lo;                                      // lo of every site: the window kernel's word to the sum kernel
     int32_t tile = SMO_TILE_DEFAULT, chunk = SMO_CHUNK_DEFAULT, batch = SMO_BATCH_DEFAULT, grid = SMO_GRID_DEFAULT;
 };
 
 static size_t smo_lds_bytes(int32_t chunk, int32_t batch) { return (size_t)chunk * (16u * (size_t)batch + 4u); }
 
-extern "C" int md_smooth_open(int device, md_smooth **out) {
-    if(!out) return fail(MD_SMOOTH_ERR_ARG, "md_smooth_open", hipSuccess);
-    *out = nullptr;
-    SMOCHK(hipSetDevice(device));
-    md_smooth *h = new md_smooth();
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
-    if(e == hipSuccess) e = hipMalloc((void **)&h->d_st, sizeof(SmoothStatus));
-    if(e == hipSuccess) e = hipHostMalloc((void **)&h->pin, sizeof(SmoothStatus), hipHostMallocDefault);
-    if(e != hipSuccess) { md_smooth_close(h); return fail(MD_SMOOTH_ERR_NOMEM, "md_smooth_open", e); }
-    *out = h;
-    return 0;
-}
+extern "C" int md_smooth_open(int device, md_smooth **out) { return side_open(device, out, "md_smooth_open", md_smooth_close); }
 
 extern "C" void md_smooth_close(md_smooth *h) {
     if(!h) return;
-    (void)hipSetDevice(h->device);
-    if(h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    (void)hipFree(h->d_st); (void)hipFree(h->d_lo);
-    if(h->pin) (void)hipHostFree(h->pin);
+    h->close(); h->d_lo.release();
     delete h;
 }
 
@@ -224,22 +205,15 @@ extern "C" int md_smooth_run(md_smooth *h, const int32_t *contig, const int32_t 
         return MD_SMOOTH_ERR_ARG;
     }
     if(!n) return 0;
-    SMOCHK(hipSetDevice(h->device));
-    if(n > h->lo_cap) {
-        (void)hipFree(h->d_lo); h->d_lo = nullptr; h->lo_cap = 0;
-        const hipError_t e = hipMalloc((void **)&h->d_lo, (size_t)n * sizeof(int32_t));
-        if(e != hipSuccess) return fail(MD_SMOOTH_ERR_NOMEM, "md_smooth_run: the windows' scratch", e);
-        h->lo_cap = n;
-    }
-    h->pin->first = ~0ull;
-    SMOCHK(hipMemcpyAsync(h->d_st, h->pin, sizeof(SmoothStatus), hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipSetDevice(h->device));
+    if(int rc = h->d_lo.need((size_t)n, "md_smooth_run: the windows' scratch")) return rc;
+    SIDE_STATUS_UP(h, h->pin, SmoothStatus);
     const KSmooth K = smo_arguments(h, contig, start, nmeth, nunmeth, n_samples, n, half_bases, min_sites, kernel, level, depth, nsites, half);
     smo_launch_window(h, K);
-    SMOCHK(hipGetLastError());
+    SIDECHK(hipGetLastError());
     smo_launch_sum(h, K, elem_bytes);
-    SMOCHK(hipGetLastError());
-    SMOCHK(hipMemcpyAsync(h->pin, h->d_st, sizeof(SmoothStatus), hipMemcpyDeviceToHost, h->st));
-    SMOCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDE_STATUS_DOWN(h, h->pin, SmoothStatus);
     const unsigned long long first = h->pin->first;
     if(first == ~0ull) return 0;
     const uint32_t bit = 1u << (first & 0xffu);

@@ -180,20 +180,16 @@ __global__ __launch_bounds__(TBX_WG) void k_tbx_newlines(const uint8_t *text, in
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512];
+#define SIDE_ERR_ARG MD_INDEX_ERR_ARG
+#define SIDE_ERR_HIP MD_INDEX_ERR_HIP
+#define SIDE_ERR_NOMEM MD_INDEX_ERR_NOMEM
+#include "mdk_side.hpp"
 extern "C" const char *md_index_last_error(void) { return g_err; }
-static int fail(int rc, const char *what, hipError_t e) {
-    if(e != hipSuccess) snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); else snprintf(g_err, sizeof g_err, "%s", what);
-    return rc;
-}
-#define TBXCHK(x) do { const hipError_t e_ = (x); if(e_ != hipSuccess) return fail(MD_INDEX_ERR_HIP, #x, e_); } while(0)
 
-struct md_index {
-    int device = 0; hipStream_t st = nullptr;
+struct md_index : SideStream {
     tbx_builder B;
     TbxStatus *d_st = nullptr; TbxStatus h_st;
-    uint4 *d_btot = nullptr, *d_boff = nullptr; uint32_t cap_blocks = 0, cap_offsets = 0;
-    tbx_rec *d_recs = nullptr; uint8_t *d_names = nullptr; uint32_t cap_recs = 0, cap_names = 0;
+    SideBuf<uint4> d_btot, d_boff; SideBuf<tbx_rec> d_recs; SideBuf<uint8_t> d_names;
     uint8_t *d_carry = nullptr; int cur = 0; uint32_t carry_len = 0;
     int64_t offset = 0, lines = 0, entries = 0, records = 0, names = 0, pieces = 0;
     uint64_t last_end = 0; uint32_t skip_left = 0;
@@ -202,26 +198,19 @@ struct md_index {
     std::vector<uint8_t> payload;
 };
 
-template<class T> static int reserve(T *&p, uint32_t &cap, uint32_t want, const char *what) {
-    if(want <= cap) return 0;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    const size_t n = (size_t)want + want / 4 + 64;
-    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-    if(e != hipSuccess) { p = nullptr; return fail(MD_INDEX_ERR_NOMEM, what, e); }
-    cap = (uint32_t)n;
-    return 0;
-}
+// room for what a piece asks and a quarter more
+template <class T> static int reserve(SideBuf<T> &b, uint32_t want, const char *what) { return b.need(want, (size_t)want + want / 4 + 64, what); }
 
 extern "C" int md_index_open(int device, const md_index_conf *conf, md_index **out) {
     if(!conf || !out || conf->col_seq < 1 || conf->col_beg < 1 || conf->col_end < 1 || conf->col_seq > 64 || conf->col_beg > 64 || conf->col_end > 64 || conf->skip < 0 ||
        conf->meta < 0 || conf->meta > 255 || (conf->format & ~TBX_UCSC) != 0)
         return fail(MD_INDEX_ERR_ARG, "md_index_open: columns from 1 to 64, meta a byte, skip not negative, format 0 or 0x10000", hipSuccess);
     *out = nullptr;
-    TBXCHK(hipSetDevice(device));
+    SIDECHK(hipSetDevice(device));
     md_index *h = new md_index();
-    h->device = device; h->skip_left = (uint32_t)conf->skip;
+    h->skip_left = (uint32_t)conf->skip;
     h->B.cf = tbx_conf{conf->format, conf->col_seq, conf->col_beg, conf->col_end, conf->meta, conf->skip};
-    hipError_t e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
+    hipError_t e = h->open(device);
     if(e == hipSuccess) e = hipMalloc((void **)&h->d_st, sizeof(TbxStatus));
     if(e == hipSuccess) e = hipMalloc((void **)&h->d_carry, 2 * TBX_MAX_LINE);
     if(e != hipSuccess) { md_index_close(h); return fail(MD_INDEX_ERR_NOMEM, "md_index_open", e); }
@@ -231,9 +220,8 @@ extern "C" int md_index_open(int device, const md_index_conf *conf, md_index **o
 
 extern "C" void md_index_close(md_index *h) {
     if(!h) return;
-    (void)hipSetDevice(h->device);
-    if(h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    (void)hipFree(h->d_st); (void)hipFree(h->d_btot); (void)hipFree(h->d_boff); (void)hipFree(h->d_recs); (void)hipFree(h->d_names); (void)hipFree(h->d_carry);
+    h->close();
+    (void)hipFree(h->d_st); h->d_btot.release(); h->d_boff.release(); h->d_recs.release(); h->d_names.release(); (void)hipFree(h->d_carry);
     delete h;
 }
 
@@ -244,42 +232,42 @@ extern "C" int md_index_feed(md_index *h, const void *d_text, int64_t bytes) {
     if(!bytes) return 0;
     if((uintptr_t)d_text & 15u) return fail(MD_INDEX_ERR_ARG, "md_index_feed: the text must be 16-byte aligned", hipSuccess);
     if(h->open_tail) return fail(MD_INDEX_ERR_ARG, "md_index_feed: the piece before this one did not end at a line's end", hipSuccess);
-    TBXCHK(hipSetDevice(h->device));
+    SIDECHK(hipSetDevice(h->device));
     const uint32_t nb = (uint32_t)((bytes + TBX_SPAN - 1) / TBX_SPAN);
-    { const int rc = reserve(h->d_btot, h->cap_blocks, nb, "hipMalloc(block table)"); if(rc) return rc; }
-    { const int rc = reserve(h->d_boff, h->cap_offsets, nb, "hipMalloc(block offsets)"); if(rc) return rc; }
+    { const int rc = reserve(h->d_btot, nb, "hipMalloc(block table)"); if(rc) return rc; }
+    { const int rc = reserve(h->d_boff, nb, "hipMalloc(block offsets)"); if(rc) return rc; }
     memset(&h->h_st, 0, sizeof h->h_st);
     h->h_st.refusal = ~0ull; h->h_st.skip_left = h->skip_left;
-    TBXCHK(hipMemcpyAsync(h->d_st, &h->h_st, sizeof(TbxStatus), hipMemcpyHostToDevice, h->st));
+    SIDECHK(hipMemcpyAsync(h->d_st, &h->h_st, sizeof(TbxStatus), hipMemcpyHostToDevice, h->st));
     KTbx K;
     memset(&K, 0, sizeof K);
     K.text = (const uint8_t *)d_text; K.bytes = bytes; K.offset = h->offset; K.cf = h->B.cf; K.btot = h->d_btot; K.boff = h->d_boff; K.st = h->d_st;
     K.carry_in = h->d_carry + (size_t)h->cur * TBX_MAX_LINE; K.carry_out = h->d_carry + (size_t)(h->cur ^ 1) * TBX_MAX_LINE; K.carry_len = h->carry_len; K.prev_last_end = h->last_end;
     if(h->skip_left) {
         hipLaunchKernelGGL(k_tbx_skip, dim3(1), dim3(1), 0, h->st, K.text, bytes, h->d_st);
-        TBXCHK(hipGetLastError());
-        TBXCHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
-        TBXCHK(hipStreamSynchronize(h->st));
+        SIDECHK(hipGetLastError());
+        SIDECHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
+        SIDECHK(hipStreamSynchronize(h->st));
         K.skip_rel = h->h_st.skip_rel; h->skip_left = h->h_st.skip_left;
     }
     hipLaunchKernelGGL(k_tbx<false>, dim3(nb), dim3(TBX_WG), 0, h->st, K);
     hipLaunchKernelGGL(k_tbx_scan, dim3(1), dim3(TBX_WG), 0, h->st, (const uint4 *)h->d_btot, h->d_boff, h->d_st, nb);
-    TBXCHK(hipGetLastError());
-    TBXCHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
-    TBXCHK(hipStreamSynchronize(h->st));
+    SIDECHK(hipGetLastError());
+    SIDECHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
+    SIDECHK(hipStreamSynchronize(h->st));
     const uint32_t n_lines = h->h_st.tot[0], n_entries = h->h_st.tot[1], n_recs = h->h_st.tot[2], n_names = h->h_st.tot[3];
     unsigned long long refusal = h->h_st.refusal;
     std::vector<tbx_rec> recs(n_recs); std::vector<uint8_t> names((size_t)n_names * TBX_NAME_SLOT);
     if(n_entries) {
-        { const int rc = reserve(h->d_recs, h->cap_recs, n_recs, "hipMalloc(records)"); if(rc) return rc; }
-        { const int rc = reserve(h->d_names, h->cap_names, n_names * TBX_NAME_SLOT, "hipMalloc(names)"); if(rc) return rc; }
+        { const int rc = reserve(h->d_recs, n_recs, "hipMalloc(records)"); if(rc) return rc; }
+        { const int rc = reserve(h->d_names, n_names * TBX_NAME_SLOT, "hipMalloc(names)"); if(rc) return rc; }
         K.recs = h->d_recs; K.names = h->d_names; K.cap_recs = n_recs; K.cap_names = n_names; K.n_entries = n_entries;
         hipLaunchKernelGGL(k_tbx<true>, dim3(nb), dim3(TBX_WG), 0, h->st, K);
-        TBXCHK(hipGetLastError());
-        if(n_recs) TBXCHK(hipMemcpyAsync(recs.data(), h->d_recs, (size_t)n_recs * sizeof(tbx_rec), hipMemcpyDeviceToHost, h->st));
-        if(n_names) TBXCHK(hipMemcpyAsync(names.data(), h->d_names, names.size(), hipMemcpyDeviceToHost, h->st));
-        TBXCHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
-        TBXCHK(hipStreamSynchronize(h->st));
+        SIDECHK(hipGetLastError());
+        if(n_recs) SIDECHK(hipMemcpyAsync(recs.data(), h->d_recs, (size_t)n_recs * sizeof(tbx_rec), hipMemcpyDeviceToHost, h->st));
+        if(n_names) SIDECHK(hipMemcpyAsync(names.data(), h->d_names, names.size(), hipMemcpyDeviceToHost, h->st));
+        SIDECHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
+        SIDECHK(hipStreamSynchronize(h->st));
         if(h->h_st.changed) return fail(MD_INDEX_ERR_ARG, "md_index_feed: the text is not the one that was measured", hipSuccess);
         uint32_t ni = 0;
         for(uint32_t i = 0; i < n_recs; i++) {
@@ -292,11 +280,11 @@ extern "C" int md_index_feed(md_index *h, const void *d_text, int64_t bytes) {
     if(refusal != ~0ull) {
         const int64_t rel = (int64_t)(refusal >> 8) - h->offset;          // the refused line starts here in this piece
         h->h_st.newlines = 0;
-        TBXCHK(hipMemcpyAsync(h->d_st, &h->h_st, sizeof(TbxStatus), hipMemcpyHostToDevice, h->st));
+        SIDECHK(hipMemcpyAsync(h->d_st, &h->h_st, sizeof(TbxStatus), hipMemcpyHostToDevice, h->st));
         if(rel > 0) hipLaunchKernelGGL(k_tbx_newlines, dim3((uint32_t)((rel + 65535) / 65536)), dim3(TBX_WG), 0, h->st, K.text, rel, h->d_st);
-        TBXCHK(hipGetLastError());
-        TBXCHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
-        TBXCHK(hipStreamSynchronize(h->st));
+        SIDECHK(hipGetLastError());
+        SIDECHK(hipMemcpyAsync(&h->h_st, h->d_st, sizeof(TbxStatus), hipMemcpyDeviceToHost, h->st));
+        SIDECHK(hipStreamSynchronize(h->st));
         h->refused = true; h->refused_line = h->lines + (int64_t)h->h_st.newlines + 1; h->refused_code = (int)(refusal & 0xff);
         if(h->refused_code == TBX_E_RETURN) snprintf(g_err, sizeof g_err, "line %lld: not sorted: contig %s appears in two places", (long long)h->refused_line, h->B.returned_name.c_str());
         else snprintf(g_err, sizeof g_err, "line %lld: %s", (long long)h->refused_line, tbx_error_text(h->refused_code));
@@ -305,7 +293,7 @@ extern "C" int md_index_feed(md_index *h, const void *d_text, int64_t bytes) {
     if(n_entries) { h->cur ^= 1; h->carry_len = h->h_st.carry_len; h->last_end = h->h_st.last_end; }
     {
         uint8_t last = 0;
-        TBXCHK(hipMemcpy(&last, K.text + bytes - 1, 1, hipMemcpyDeviceToHost));
+        SIDECHK(hipMemcpy(&last, K.text + bytes - 1, 1, hipMemcpyDeviceToHost));
         h->open_tail = last != '\n';
     }
     h->offset += bytes; h->lines += n_lines; h->entries += n_entries; h->records += n_recs; h->names += n_names; h->pieces++;

@@ -164,8 +164,8 @@ def test_ranges_that_begin_and_end_anywhere(emu):
     index_at = int(np.frombuffer(whole, "<u8", 1, 24)[0])
     ranges = [(0, 1), (3, 70), (60, 300), (index_at - 5, 60), (index_at + 40, 9), (len(whole) - 1, 1), (len(whole) - 9, 9), (1, len(whole) - 2), (17, 0)]
     assert f["levels"] >= 1
-    with mdk._track_lock:
-        h = mdk._track_handle(L, 0)
+    with mdk._side_locks["track"]:
+        h = mdk._side_handle(L, "track", 0)
         for at, n in ranges:
             buf = torch.full((n + 16,), 0xA5, dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
