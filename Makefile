@@ -40,10 +40,10 @@ $(eval $(call side_lib,stats,mdk_qdiff.hip,$(CSRC)/mdk_qdiff_core.h $(CSRC)/mdk_
 $(eval $(call side_lib,track,mdk_bigwig.hip,$(CSRC)/mdk_bigwig_core.h $(CSRC)/mdk_deflate_core.h include/mdk_track.h))
 # smoothing (the first smooth call): mdk_smooth_core.h's MDK_SMO_NO_CONTRACT keeps the products unfused
 $(eval $(call side_lib,smooth,mdk_smooth.hip,$(CSRC)/mdk_smooth_core.h include/mdk_smooth.h))
-# the united table as text and back (the first Cohort.write / render / read call)
-$(eval $(call side_lib,cohort,mdk_cohort.hip,$(CSRC)/mdk_cohort_core.h $(CSRC)/mdk_text_core.h $(CSRC)/mdk_parse_core.h include/mdk_cohort.h))
+# the united table as text and back, and its sums over intervals (the first Cohort.write / render / read / regions call)
+$(eval $(call side_lib,cohort,mdk_cohort.hip,$(CSRC)/mdk_cohort_core.h $(CSRC)/mdk_text_core.h $(CSRC)/mdk_parse_core.h $(CSRC)/mdk_cregion.hip $(CSRC)/mdk_cregion_core.h $(CSRC)/mdk_region_core.h include/mdk_cohort.h))
 
-tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/cohort_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
+tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/cohort_emu tools/_build/cregion_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
 	@mkdir -p tools/_build
 	$(CC) -O2 -g -Wall -shared -fPIC -Iinclude -o $@ tools/piece_standin.c -lz
@@ -98,6 +98,9 @@ tools/_build/smooth_emu: tools/smooth_emu.cpp methyldackel_amd/csrc/mdk_smooth_c
 tools/_build/cohort_emu: tools/cohort_emu.cpp methyldackel_amd/csrc/mdk_cohort_core.h methyldackel_amd/csrc/mdk_text_core.h methyldackel_amd/csrc/mdk_parse_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -o $@ tools/cohort_emu.cpp -Imethyldackel_amd/csrc
+tools/_build/cregion_emu: tools/cregion_emu.cpp methyldackel_amd/csrc/mdk_cregion_core.h methyldackel_amd/csrc/mdk_region_core.h
+	@mkdir -p tools/_build
+	g++ -O2 -Wall -o $@ tools/cregion_emu.cpp -Imethyldackel_amd/csrc
 tools/_build/smooth_bench: tools/smooth_bench.hip methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/smooth_bench.hip

@@ -1,5 +1,5 @@
 /* mdk_cohort.h -- libmdk_cohort.so (csrc/mdk_cohort.hip): a united table (n sites, S samples, counts [S, n]) written as text and read
- * back on the device.  The formats and the refusals are csrc/mdk_cohort_core.h's.  A library of its own: it links none of the others.
+ * back on the device, and every sample's sums over intervals (csrc/mdk_cregion.hip).  The formats and the refusals are csrc/mdk_cohort_core.h's.  A library of its own: it links none of the others.
  * Every pointer but the names, `out` results and error text is DEVICE memory; every call is synchronous; a handle's calls come from one
  * thread at a time.  Return 0, or MD_COHORT_ERR_*; md_cohort_last_error() says more. */
 #ifndef MDK_COHORT_H
@@ -40,6 +40,19 @@ int md_cohort_parse_measure(md_cohort *h, const void *text, int64_t bytes, int64
 int md_cohort_parse_fill(md_cohort *h, const md_cohort_sites *sites, int32_t *nmeth, int32_t *nunmeth, int64_t stride, int64_t row_at, int64_t rows,
                          int has_prev, int32_t prev_contig, int32_t prev_start);
 int64_t md_cohort_parse_error_offset(md_cohort *h);
+
+/* sums over intervals (csrc/mdk_cregion.hip; the rule is csrc/mdk_region_core.h's, applied to every sample): the table's four site
+ * columns the rule reads (int32 contig and start, uint8 context, int8 strand; rows strictly ascending in (contig, start)), nmeth and
+ * nunmeth [n_samples, n] contiguous, k half-open intervals in any order, and the filter -- bit t of context_mask for context t; bit 0,
+ * 1, 2 of strand_mask for strand +1, -1, 0; a cell counts with nmeth + nunmeth >= min_depth.  The results are [n_samples, k]
+ * contiguous: cell (s, j) holds what md_text_regions gives for sample s and interval j.  The contig count is md_cohort_names'.  A row
+ * that does not ascend, a row's contig outside the names or context above 2, an interval's contig outside the names, start < 0 or end <
+ * start are MD_COHORT_ERR_ARG; the results are then undefined.  It leaves a measure that waits for its fill as it is. */
+int md_cohort_regions(md_cohort *h, const void *contig, const void *start, const void *context, const void *strand,
+                      const int32_t *nmeth, const int32_t *nunmeth, int32_t n_samples, int64_t n,
+                      const int32_t *iv_contig, const int32_t *iv_start, const int32_t *iv_end, int64_t k,
+                      uint32_t context_mask, uint32_t strand_mask, int32_t min_depth,
+                      int32_t *nsites, int64_t *out_nmeth, int64_t *out_nunmeth);
 #ifdef __cplusplus
 }
 #endif

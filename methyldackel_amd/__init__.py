@@ -27,7 +27,7 @@ LIB_EXTRACT = BUILD / "libmdk_extract.so"
 LIB_INDEX = BUILD / "libmdk_index.so"                          # tabix indexes: a library of its own, loaded at the first index call
 LIB_STATS = BUILD / "libmdk_stats.so"                          # the replicates' F test: likewise, loaded at the first diff_replicates call
 LIB_SMOOTH = BUILD / "libmdk_smooth.so"                        # smoothing: likewise, loaded at the first smooth call
-LIB_COHORT = BUILD / "libmdk_cohort.so"                        # the united table as text: likewise, loaded at the first Cohort.write / render / read call
+LIB_COHORT = BUILD / "libmdk_cohort.so"                        # the united table as text and its sums over intervals: likewise, loaded at the first Cohort.write / render / read / regions call
 LIB_TRACK = BUILD / "libmdk_track.so"                         # the bigWig track: likewise, loaded at the first render_bigwig / write_bigwig call
 CLI = BUILD / "MethylDackel"
 
@@ -817,6 +817,43 @@ def bgzf_compress(data, eof=True):
     return _deflate(L, _BGZF_RENDERERS[k], data, eof)
 
 
+def _region_filter(contigs, intervals, contexts, strand, min_depth):
+    """what ``Calls.regions``, ``Cytosines.regions`` and ``Cohort.regions`` ask, checked before a tensor is looked at:
+    (context_mask, strand_mask, min_depth) as csrc/mdk_region_core.h takes them"""
+    if not isinstance(intervals, Intervals):
+        raise MdkError("regions needs an Intervals (Intervals.read, Intervals.windows)")
+    if list(intervals.contigs) != list(contigs):
+        raise MdkError("the intervals' contigs are not the rows' contigs: their indices would name other sequences")
+    if contexts is None:
+        contexts = (0, 1, 2)
+    context_mask = 0
+    for x in ([contexts] if isinstance(contexts, (str, int)) else contexts):
+        if x in CONTEXT_FILES:
+            x = CONTEXT_FILES.index(x)
+        if isinstance(x, bool) or x not in (0, 1, 2):
+            raise MdkError(f"unknown context {x!r}: a subset of {CONTEXT_FILES}, or of the indices 0 to 2")
+        context_mask |= 1 << x
+    if strand not in (None, "+", "-"):
+        raise MdkError(f"unknown strand {strand!r}: None (any), '+' or '-'")
+    strand_mask = {None: 7, "+": 1, "-": 2}[strand]
+    min_depth = int(min_depth)
+    if not 0 <= min_depth <= 2 ** 31 - 1:
+        raise MdkError("min_depth must be between 0 and 2^31 - 1")
+    return context_mask, strand_mask, min_depth
+
+
+def _region_intervals(intervals, dev):
+    """``intervals`` on ``dev`` (itself if it is there already), its three columns checked"""
+    import torch
+    iv = intervals.to(dev)
+    k = len(iv)
+    for name in ("contig", "start", "end"):
+        t = getattr(iv, name)
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != k:
+            raise MdkError(f"the intervals' {name} column must be a contiguous int32 tensor with one entry per interval")
+    return iv
+
+
 class _Columns:
     """what a session run returns: ``contigs`` (names, BAM header order) and one tensor attribute per entry of COLUMNS"""
     COLUMNS = ()
@@ -911,37 +948,15 @@ class _Columns:
         """the sums of ``cols`` -- this object's rows as the seven tensors of CALL_COLUMNS -- over ``intervals`` on the rows' device
         (k_region_rows / k_region_blocks / k_region_sum, csrc/mdk_regions.hip): a Regions of the intervals' tensors and three new ones"""
         import torch
-        if not isinstance(intervals, Intervals):
-            raise MdkError("regions needs an Intervals (Intervals.read, Intervals.windows)")
-        if list(intervals.contigs) != list(self.contigs):
-            raise MdkError("the intervals' contigs are not the rows' contigs: their indices would name other sequences")
-        if contexts is None:
-            contexts = (0, 1, 2)
-        context_mask = 0
-        for x in ([contexts] if isinstance(contexts, (str, int)) else contexts):
-            if x in CONTEXT_FILES:
-                x = CONTEXT_FILES.index(x)
-            if isinstance(x, bool) or x not in (0, 1, 2):
-                raise MdkError(f"unknown context {x!r}: a subset of {CONTEXT_FILES}, or of the indices 0 to 2")
-            context_mask |= 1 << x
-        if strand not in (None, "+", "-"):
-            raise MdkError(f"unknown strand {strand!r}: None (any), '+' or '-'")
-        strand_mask = {None: 7, "+": 1, "-": 2}[strand]
-        min_depth = int(min_depth)
-        if not 0 <= min_depth <= 2 ** 31 - 1:
-            raise MdkError("min_depth must be between 0 and 2^31 - 1")
+        context_mask, strand_mask, min_depth = _region_filter(self.contigs, intervals, contexts, strand, min_depth)
         dev, n = cols[0].device, int(cols[0].shape[0])
         for t, (name, dt) in zip(cols, CALL_COLUMNS):
             if t.device.type != "cuda":
                 raise MdkError(f"regions are summed on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
             if t.device != dev or t.dtype != getattr(torch, dt) or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != n:
                 raise MdkError(f"the {name} column must be a contiguous {dt} tensor on {dev} with one entry per row")
-        iv = intervals.to(dev)
+        iv = _region_intervals(intervals, dev)
         k = len(iv)
-        for name in ("contig", "start", "end"):
-            t = getattr(iv, name)
-            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] != k:
-                raise MdkError(f"the intervals' {name} column must be a contiguous int32 tensor with one entry per interval")
         L = self._renderer(dev)
         out = {"contig": iv.contig, "start": iv.start, "end": iv.end, "nsites": torch.empty(k, dtype=torch.int32, device=dev),
                "nmeth": torch.empty(k, dtype=torch.int64, device=dev), "nunmeth": torch.empty(k, dtype=torch.int64, device=dev)}
@@ -2476,6 +2491,53 @@ class Cohort:
         out = smooth_counts(self.contig, self.start, self.nmeth, self.nunmeth, half_bases, min_sites, kernel)
         return Smoothed(self.contigs, {name: getattr(self, name) for name, _ in SITE_COLUMNS}, *out, half_bases, min_sites, kernel, merged=self.merged)
 
+    def regions(self, intervals, contexts=None, strand=None, min_depth=1):
+        """Every sample's sums over ``intervals`` in one pass on the device -- methylKit's ``tileMethylCounts`` on a united object; CpG
+        islands, promoters, tiles (``Intervals.windows``) or the regions ``Diff.dmrs`` has just reported (``dmrs.intervals()``).  The
+        arguments are ``Calls.regions``': an ``Intervals`` over the same ``contigs``, a subset of the contexts by name or index,
+        ``strand`` None, ``"+"`` or ``"-"``, and ``min_depth`` (0 to 2^31 - 1), which cuts CELL by cell: site i counts for sample s if its
+        context and strand pass and ``nmeth[s, i] + nunmeth[s, i] >= min_depth`` (formed in 64 bits).  A ``CohortRegions`` whose
+        ``nsites`` (int32), ``nmeth`` and ``nunmeth`` (int64) are ``[S, k]`` in the intervals' own order: cell (s, j) is, by definition
+        and bit for bit, what ``cohort.sample(s).regions(intervals, contexts, strand, min_depth)`` gives for interval j -- without the
+        loop, its S checks of the same rows, its S searches per interval and the ``torch.stack`` behind it (csrc/mdk_cregion.hip:
+        k_cregion_sites, k_cregion_ranges, k_cregion_totals, k_cregion_scan, k_cregion_sum).  The matrices go as they come into
+        ``mdk.diff_counts(r.nmeth, r.nunmeth, a, b)`` and ``mdk.diff_replicates(r.nmeth, r.nunmeth, a, b)``: the test of the regions.
+        An empty table, no intervals, empty intervals and intervals without rows give zeros.  Rows that are not strictly ascending, a
+        row's contig outside the names or context above 2, an interval's contig outside the names, ``start < 0`` or ``end < start``
+        raise MdkError (rc -3); so do, before the library is touched, CPU tensors (there is no CPU path), matrices that are not
+        contiguous int32 ``[S, n]`` on the site columns' device, S outside 1 to 1024, more than 2^30 sites or intervals, and intervals
+        over other contigs."""
+        import torch
+        context_mask, strand_mask, min_depth = _region_filter(self.contigs, intervals, contexts, strand, min_depth)
+        S, n = int(self.nmeth.shape[0]) if self.nmeth.dim() == 2 else -1, len(self)
+        if not 1 <= S <= MAX_SAMPLES:
+            raise MdkError(f"regions are summed for 1 to {MAX_SAMPLES} samples: nmeth must be a [samples, sites] tensor")
+        tensors = [(name, getattr(self, name), dt, (n,)) for name, dt in SITE_COLUMNS if name in ("contig", "start", "context", "strand")]
+        tensors += [("nmeth", self.nmeth, "int32", (S, n)), ("nunmeth", self.nunmeth, "int32", (S, n))]
+        for name, t, dt, shape in tensors:
+            if t.dtype != getattr(torch, dt) or tuple(t.shape) != shape or not t.is_contiguous():
+                raise MdkError(f"the {name} column must be a contiguous {dt} tensor of shape {shape}")
+        for name, t, dt, shape in tensors:
+            if t.device.type != "cuda":
+                raise MdkError(f"regions are summed on the device: the {name} column is a {t.device.type} tensor, and there is no CPU path")
+        dev = self.start.device
+        for name, t, dt, shape in tensors:
+            if t.device != dev:
+                raise MdkError(f"the {name} column must be on the site columns' device, {dev}")
+        iv = _region_intervals(intervals, dev)
+        k = len(iv)
+        if n > MAX_INTERVALS or k > MAX_INTERVALS:
+            raise MdkError(f"{n} sites and {k} intervals: more than 2^30")
+        out = [torch.empty((S, k), dtype=dt, device=dev) for dt in (torch.int32, torch.int64, torch.int64)]
+        L = lib_cohort()
+        torch.cuda.current_stream(dev).synchronize()             # the columns are complete, and nothing of torch's is queued on memory it hands out next
+        with _side_locks["cohort"]:                              # a handle per device, kept: its calls come from one thread at a time
+            h = _cohort_handle(L, dev.index or 0, self.contigs)
+            _side_call(L, "cohort", "regions", h, *[C.c_void_p(t.data_ptr()) for _, t, _, _ in tensors], S, n,
+                       *[C.c_void_p(getattr(iv, name).data_ptr()) for name in ("contig", "start", "end")], k, context_mask, strand_mask, min_depth,
+                       *[C.c_void_p(t.data_ptr()) for t in out])
+        return CohortRegions(list(self.contigs), iv.contig, iv.start, iv.end, *out, names=self.names)
+
     # ---- the table as text and back (include/mdk_cohort.h, csrc/mdk_cohort.hip -> libmdk_cohort.so; the formats are csrc/mdk_cohort_core.h's) ----
     def _text_arguments(self, fmt, names, piece_bytes):
         """what ``write`` and ``render`` ask, checked before the library is touched or a file opened: (format code, header bytes, piece_bytes, device)"""
@@ -2635,6 +2697,61 @@ class Cohort:
             cols = {name: torch.empty(0, dtype=getattr(torch, dt), device=dev) for name, dt in SITE_COLUMNS}
             m, u = (torch.empty((S, 0), dtype=torch.int32, device=dev) for _ in range(2))
         return cls(contigs, cols, m, u, merged, contexts_on, n_union, names)
+
+
+class CohortRegions:
+    """What ``Cohort.regions`` returns, on the table's device: ``contig``, ``start``, ``end`` (int32, one entry per interval: the
+    intervals' own tensors, in their own order) and the matrices ``nsites`` (int32), ``nmeth`` and ``nunmeth`` (int64), ``[S, k]``
+    contiguous, row s the sums of sample s.  ``contigs`` are the table's and ``names`` its sample names (or None).  There is no
+    ``diff`` here: ``mdk.diff_counts(r.nmeth, r.nunmeth, a, b)`` and ``mdk.diff_replicates(r.nmeth, r.nunmeth, a, b)`` take the
+    matrices as they come."""
+
+    def __init__(self, contigs, contig, start, end, nsites, nmeth, nunmeth, names=None):
+        self.contigs = contigs
+        self.contig, self.start, self.end = contig, start, end
+        self.nsites, self.nmeth, self.nunmeth = nsites, nmeth, nunmeth
+        self.names = None if names is None else _cohort_sample_names(names, int(nmeth.shape[0]))
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    @property
+    def n_samples(self):
+        return int(self.nmeth.shape[0])
+
+    def select(self, index):
+        """a copy with the intervals ``column[index]`` (a boolean mask, an index tensor, a slice): of the three interval columns, and of
+        the matrices along their interval axis"""
+        return CohortRegions(self.contigs, *[t[index].contiguous() for t in (self.contig, self.start, self.end)],
+                             *[t[:, index].contiguous() for t in (self.nsites, self.nmeth, self.nunmeth)], names=self.names)
+
+    def sample(self, i):
+        """sample ``i`` as a ``Regions``: the interval columns and row ``i`` of the three matrices -- views, not copies"""
+        i = int(i)
+        if not 0 <= i < self.n_samples:
+            raise MdkError(f"sample {i}: the result holds samples 0 to {self.n_samples - 1}")
+        return Regions(self.contigs, {"contig": self.contig, "start": self.start, "end": self.end, "nsites": self.nsites[i], "nmeth": self.nmeth[i], "nunmeth": self.nunmeth[i]})
+
+    def intervals(self):
+        """the intervals as an ``Intervals`` (the same tensors)"""
+        return Intervals(self.contigs, self.contig, self.start, self.end)
+
+    def rows(self):
+        """(chrom, start, end, (nsites, nmeth, nunmeth) of sample 0, of sample 1, ...) tuples on the host"""
+        cols = [t.cpu().tolist() for t in (self.contig, self.start, self.end)]
+        k, m, u = (t.t().cpu().tolist() for t in (self.nsites, self.nmeth, self.nunmeth))
+        return [(self.contigs[c], a, b) + tuple(zip(kk, mm, uu)) for (c, a, b), kk, mm, uu in zip(zip(*cols), k, m, u)]
+
+    def write(self, path, names=None):
+        """One ``#chrom start end NAME.nsites NAME.nmeth NAME.nunmeth ...`` line, then a line per interval, tab-separated, the contig by
+        its name; formatted on the host, as ``Regions.write``.  ``names``: the samples' names (default ``self.names``, or ``s0`` ...).
+        Returns the path."""
+        S = self.n_samples
+        names = _cohort_sample_names(names if names is not None else self.names if self.names is not None else [f"s{i}" for i in range(S)], S)
+        with open(path, "w") as f:
+            f.write("\t".join(["#chrom", "start", "end"] + [f"{v}.{w}" for v in names for w in ("nsites", "nmeth", "nunmeth")]) + "\n")
+            f.writelines("\t".join([r[0]] + [str(v) for v in r[1:3]] + [str(v) for cell in r[3:] for v in cell]) + "\n" for r in self.rows())
+        return path
 
 
 DIFF_SITE_COLUMNS = (("contig", "int32"), ("start", "int32"), ("end", "int32"), ("context", "uint8"), ("strand", "int8"))
@@ -2860,7 +2977,7 @@ class md_cohort_sites(C.Structure):
 
 
 def lib_cohort():
-    """libmdk_cohort.so, loaded at the first ``Cohort.write`` / ``render`` / ``read`` call: its code object's load is paid there and by no command"""
+    """libmdk_cohort.so, loaded at the first ``Cohort.write`` / ``render`` / ``read`` / ``regions`` call: its code object's load is paid there and by no command"""
     global _cohort
     if _cohort is None:
         L = _load_side("cohort", LIB_COHORT, "cohort text")
@@ -2872,6 +2989,7 @@ def lib_cohort():
         L.md_cohort_parse_measure.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         L.md_cohort_parse_fill.argtypes = [C.c_void_p, C.POINTER(md_cohort_sites), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32]
         L.md_cohort_parse_error_offset.argtypes = [C.c_void_p]; L.md_cohort_parse_error_offset.restype = C.c_int64
+        L.md_cohort_regions.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_uint32, C.c_uint32, C.c_int32] + [C.c_void_p] * 3
         _cohort = L
     return _cohort
 
@@ -2891,7 +3009,8 @@ def _cohort_handle(L, device, contigs=None):
 
 def cohort_limits(device=0, tile_sites=0, sample_block=0, max_workgroups=0):
     """A test hook (md_cohort_limits): the sites of a tile, the samples of a block and the most workgroups of a launch for the
-    ``Cohort.write`` / ``render`` / ``read`` calls on ``device`` from now on; 0 is the default of each.  No byte and no column depends on them."""
+    ``Cohort.write`` / ``render`` / ``read`` / ``regions`` calls on ``device`` from now on; 0 is the default of each.  No byte, no column and
+    no sum depends on them."""
     _side_limits(lib_cohort(), "cohort", device, tile_sites, sample_block, max_workgroups)
 
 
@@ -3070,8 +3189,8 @@ class Diff(_Columns):
         the regions is one more call, on every sample's sums over them::
 
             r = d.dmrs(d.qvalue() < 0.01)
-            per = [cohort.sample(i).regions(r.intervals()) for i in range(cohort.n_samples)]
-            test = mdk.diff_replicates(torch.stack([p.nmeth for p in per]), torch.stack([p.nunmeth for p in per]), a, b)"""
+            per = cohort.regions(r.intervals())
+            test = mdk.diff_replicates(per.nmeth, per.nunmeth, a, b)"""
         import math
         import torch
         names = [n for n, _ in DIFF_SITE_COLUMNS[:3] + DIFF_RESULT_COLUMNS[:4]]

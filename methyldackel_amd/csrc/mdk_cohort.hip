@@ -27,6 +27,8 @@
 // Whatever a text or a table holds, nothing outside the buffers is touched: a stretch outside the text is read byte by byte inside it, a
 // field index past the last column is never stored, a refused table is never filled.  Plain C++, vector loads and stores, no atomics but
 // the status word's and the span counters' in LDS.
+// SUMS OVER INTERVALS (md_cohort_regions) are csrc/mdk_cregion.hip, included at the end of this file: they use this handle's stream, status
+// word, contig count and limits, and temporaries of their own beside the ones above.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -331,6 +333,7 @@ struct md_cohort : SideHandle<CohStatus> {
     KCohW W; bool measured = false; int64_t total = 0;
     SideBuf<int64_t> d_cnt, d_line;
     KCohR P; bool counted = false; int64_t err_offset = -1;
+    SideBuf<uint8_t> d_rpass; SideBuf<uint32_t> d_rlo, d_rhi, d_rsites; SideBuf<int64_t> d_rm, d_ru;      // md_cohort_regions' (mdk_cregion.hip), kept likewise
 };
 
 extern "C" int md_cohort_open(int device, md_cohort **out) {
@@ -342,6 +345,7 @@ extern "C" void md_cohort_close(md_cohort *h) {
     h->close();
     (void)hipFree(h->d_name_off); (void)hipFree(h->d_sorted); (void)hipFree(h->d_names);
     h->d_len.release(); h->d_part.release(); h->d_cnt.release(); h->d_line.release();
+    h->d_rpass.release(); h->d_rlo.release(); h->d_rhi.release(); h->d_rsites.release(); h->d_rm.release(); h->d_ru.release();
     if(h->pin64) (void)hipHostFree(h->pin64);
     delete h;
 }
@@ -537,3 +541,8 @@ extern "C" int md_cohort_parse_fill(md_cohort *h, const md_cohort_sites *sites, 
 }
 
 extern "C" int64_t md_cohort_parse_error_offset(md_cohort *h) { return h ? h->err_offset : -1; }
+
+// ------------------------------------------------------------------------------------------------
+// every sample's sums over intervals
+// ------------------------------------------------------------------------------------------------
+#include "mdk_cregion.hip"
