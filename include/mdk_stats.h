@@ -1,5 +1,6 @@
 /* mdk_stats.h -- the C ABI of libmdk_stats.so: two groups of REPLICATE samples compared site by site on the device, the quasi-binomial F
- * test of csrc/mdk_qdiff_core.h (csrc/mdk_qdiff.hip; entries, limits and refusals are csrc/mdk_diff_core.h's).  A library of its own, as
+ * test of csrc/mdk_qdiff_core.h (csrc/mdk_qdiff.hip; entries, limits and refusals are csrc/mdk_diff_core.h's) -- and how alike the samples
+ * of a table are, the pairwise sample moments of csrc/mdk_moments_core.h (csrc/mdk_moments.hip, the same source).  A library of its own, as
  * libmdk_index.so is: one code object, its own stream, its own pinned status block and its own error text, and no link dependency on
  * libmdk_hip.so or libmdk_extract.so.
  *
@@ -31,6 +32,9 @@ int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmeth, int elem
                    const int32_t *order, int32_t n_a, int32_t n_b, double min_dispersion,
                    int64_t *nmeth_a, int64_t *nunmeth_a, int64_t *nmeth_b, int64_t *nunmeth_b, double *meth_diff,
                    double *pvalue, int32_t *df, double *dispersion, double *statistic, uint32_t *steps);
+
+/* The pairwise sample moments, on the same handle: three more calls, declared and documented in a header of their own */
+#include "mdk_moments.h"
 void md_stats_close(md_stats *h);
 const char *md_stats_last_error(void);
 

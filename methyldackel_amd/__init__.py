@@ -2481,6 +2481,13 @@ class Cohort:
         cols.update(zip((name for name, _ in REPLICATE_RESULT_COLUMNS), out))
         return ReplicateDiff(self.contigs, cols, merged=self.merged)
 
+    def moments(self, min_depth=1):
+        """How alike the table's samples are, the first look after ``unite`` -- methylKit's ``getCorrelation``: a ``SampleMoments`` of
+        the two matrices with the table's ``names``, made on the device by ``sample_moments``, which documents the rule.  A site a
+        sample does not hold (``0 0``) is not covered there and takes part in no pair with that sample.
+        ``cohort.moments().correlation()`` is the samples' correlation matrix, ``.distance()`` what ``clusterSamples`` clusters on."""
+        return sample_moments(self.nmeth, self.nunmeth, min_depth, names=self.names)
+
     def smooth(self, half_bases=1000, min_sites=70, kernel="tricube"):
         """Every sample's counts smoothed along the genome, the step between ``unite`` and a test or a plot at low coverage -- what
         bsseq's BSmooth and DSS's ``smoothing=TRUE`` do first: a site's window reaches at least ``half_bases`` to either side AND holds
@@ -2736,6 +2743,11 @@ class CohortRegions:
         """the intervals as an ``Intervals`` (the same tensors)"""
         return Intervals(self.contigs, self.contig, self.start, self.end)
 
+    def moments(self, min_depth=1):
+        """``Cohort.moments`` of the intervals' sums: a ``SampleMoments`` over the intervals, an interval covered for a sample if its
+        ``nmeth + nunmeth >= min_depth``.  A sum of 2^26 or more is refused, as ``diff_counts`` refuses it."""
+        return sample_moments(self.nmeth, self.nunmeth, min_depth, names=self.names)
+
     def rows(self):
         """(chrom, start, end, (nsites, nmeth, nunmeth) of sample 0, of sample 1, ...) tuples on the host"""
         cols = [t.cpu().tolist() for t in (self.contig, self.start, self.end)]
@@ -2873,6 +2885,179 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
         _side_call(L, "stats", "qdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(groups[0]), len(groups[1]),
                    float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
     return tuple(out)
+
+
+# ---- the pairwise sample moments (include/mdk_moments.h, csrc/mdk_moments.hip in libmdk_stats.so; the rule is csrc/mdk_moments_core.h) ----
+MOMENTS_WHAT = ("correlation", "covariance", "n")
+MOMENTS_SHAPES = {"auto": 0, "lanes": 1, "staged": 2}          # MOM_SHAPE_* of csrc/mdk_moments.hip
+
+
+def lib_moments():
+    """``lib_stats()``'s library with the moments' three calls bound, at the first call that needs them: the one library and the one
+    handle per device of ``diff_replicates``"""
+    L = lib_stats()
+    if "md_stats_moments" not in vars(L):
+        L.md_stats_center.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 2
+        L.md_stats_moments_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.md_stats_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_int64] + [C.c_void_p] * 4
+    return L
+
+
+def moments_limits(device=0, shape=0, chunk_sites=0, pair_tile=0, max_workgroups=0):
+    """A test hook (md_stats_moments_limits): the kernel shape (0 by S, 1 a lane per site, 2 staged in LDS; or a name of
+    ``MOMENTS_SHAPES``), the sites of a staged chunk, a lane's pairs a side and the most workgroups of a launch for the
+    ``sample_moments`` calls on ``device`` from now on; 0 is the default of each.  The results do not depend on them."""
+    L = lib_moments()
+    with _side_locks["stats"]:
+        _side_call(L, "stats", "moments_limits", _side_handle(L, "stats", int(device)), int(MOMENTS_SHAPES.get(shape, shape)), int(chunk_sites), int(pair_tile), int(max_workgroups))
+
+
+def _moments_arguments(nmeth, nunmeth, min_depth):
+    """what ``sample_moments`` asks of its arguments, checked before the library is touched, the way ``_diff_arguments`` checks: (S, n,
+    the matrices' device)"""
+    import torch
+    what = "sample_moments"
+    if isinstance(min_depth, bool) or not isinstance(min_depth, int) or not 1 <= min_depth < 1 << 26:
+        raise MdkError(f"{what}: min_depth must be an integer within 1 and 2^26 - 1, not {min_depth!r}")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous, sample-major")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if t.device.type != "cuda":
+            raise MdkError(f"moments are summed on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    if nunmeth.device != dev:
+        raise MdkError(f"{what}: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    return S, n, dev
+
+
+def _moments_center(sums):
+    """``cxy`` and ``vxx`` of the four int64 ``[S, S]`` device matrices (n, sx, sxx, sxy): md_stats_center"""
+    import torch
+    S, dev = int(sums[0].shape[0]), sums[0].device
+    out = [torch.empty((S, S), dtype=torch.float64, device=dev) for _ in range(2)]
+    L = lib_moments()
+    torch.cuda.current_stream(dev).synchronize()             # the sums are complete, and nothing of torch's is queued on memory it hands out next
+    with _side_locks["stats"]:
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "center", h, *[C.c_void_p(t.data_ptr()) for t in sums], S, *[C.c_void_p(t.data_ptr()) for t in out])
+    return out
+
+
+def sample_moments(nmeth, nunmeth, min_depth=1, names=None):
+    """How alike the samples of a table are -- what methylKit's ``getCorrelation``, ``clusterSamples`` and ``PCASamples`` start from --,
+    summed on the device (csrc/mdk_moments.hip).  ``nmeth`` and ``nunmeth`` are two ``[S, n]`` device tensors of one dtype, int32 or
+    int64, contiguous, row s the counts of sample s: a ``Cohort``'s matrices or a ``CohortRegions``'.  A cell is covered if ``nmeth +
+    nunmeth >= min_depth`` (1 to 2^26 - 1); its level is the methylated fraction in units of 2^-16, rounded half up.  A ``SampleMoments``:
+    over the sites where samples i and j are BOTH covered (pairwise-complete observations) their number ``n``, the sums ``sx`` of i's
+    levels, ``sxx`` of their squares and ``sxy`` of the products of i's and j's -- exact integers, the same bits on every run, device
+    and blocking of the kernels --, and ``cxy = n sxy - sx sx^T`` and ``vxx = n sxx - sx^2``, formed in 128-bit integers and rounded once.
+    The matrices are not changed.  A negative entry and an entry of 2^26 or more raise MdkError (rc -3) naming the first such site; so do
+    CPU tensors: there is no CPU path.  Not here: Spearman's correlation, weights by depth, PCA and clustering
+    (``torch.linalg.eigh(moments.covariance())`` is the first of them)."""
+    import torch
+    S, n, dev = _moments_arguments(nmeth, nunmeth, min_depth)
+    if names is not None:
+        names = _cohort_sample_names(names, S)
+    L = lib_moments()
+    sums = [torch.empty((S, S), dtype=torch.int64, device=dev) for _ in range(4)]
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    with _side_locks["stats"]:                               # a handle per device, kept: its calls come from one thread at a time
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "moments", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, min_depth,
+                   *[C.c_void_p(t.data_ptr()) for t in sums])
+    return SampleMoments(*sums, *_moments_center(sums), min_depth, names)
+
+
+class SampleMoments:
+    """What ``sample_moments``, ``Cohort.moments`` and ``CohortRegions.moments`` return, on the table's device: ``n``, ``sx``, ``sxx``,
+    ``sxy`` (int64 ``[S, S]``) and ``cxy``, ``vxx`` (float64 ``[S, S]``) as ``sample_moments`` documents them, ``min_depth``, and
+    ``names``, a tuple of S sample names or None.  Row i, column j is about sample i over the sites it shares with sample j; ``n``,
+    ``sxy`` and ``cxy`` are symmetric, the diagonals each sample's own.  The methods work in torch on the device from these matrices.
+    ``a + b`` is the moments of two disjoint sets of sites -- chromosomes, batches -- of the same samples: the integers add, and the
+    sum is centred again."""
+
+    def __init__(self, n, sx, sxx, sxy, cxy, vxx, min_depth=1, names=None):
+        self.n, self.sx, self.sxx, self.sxy, self.cxy, self.vxx = n, sx, sxx, sxy, cxy, vxx
+        self.min_depth = int(min_depth)
+        self.names = None if names is None else _cohort_sample_names(names, int(n.shape[0]))
+
+    @property
+    def n_samples(self):
+        return int(self.n.shape[0])
+
+    def mean(self):
+        """float64 ``[S, S]``: the mean level of sample i over the sites it shares with j, ``sx / n / 65536`` -- the correctly rounded
+        quotient, both integers being exact as doubles; NaN where n is 0"""
+        return self.sx.double() / self.n.double() / 65536.0
+
+    def covariance(self):
+        """float64 ``[S, S]``: the sample covariance of the levels as fractions, ``cxy / (n (n - 1)) / 2^32``, within 4 * 2^-53 of the
+        exact quotient; NaN where n < 2"""
+        import torch
+        n = self.n.double()
+        c = self.cxy / (n * (n - 1.0)) / 4294967296.0
+        return torch.where(self.n >= 2, c, torch.full_like(c, float("nan")))
+
+    def correlation(self):
+        """float64 ``[S, S]``: Pearson's correlation over the shared sites, ``cxy / sqrt(vxx * vxx^T)``, within 8 * 2^-53 of exact
+        arithmetic and clamped to [-1, 1]; NaN where n < 2 or either sample is constant over the shared sites; the diagonal exactly
+        1.0 where it is defined"""
+        import torch
+        vt = self.vxx.t()
+        r = torch.clamp(self.cxy / torch.sqrt(self.vxx * vt), -1.0, 1.0)
+        r = torch.where((self.n >= 2) & (self.vxx > 0) & (vt > 0), r, torch.full_like(r, float("nan")))
+        d = torch.diagonal(r)                                 # (a view)
+        d.copy_(torch.where(torch.isnan(d), d, torch.ones_like(d)))
+        return r
+
+    def distance(self):
+        """``1 - correlation()``: what methylKit's ``clusterSamples`` clusters on"""
+        return 1.0 - self.correlation()
+
+    def __add__(self, other):
+        import torch
+        if not isinstance(other, SampleMoments):
+            return NotImplemented
+        if other.n_samples != self.n_samples or other.names != self.names or other.min_depth != self.min_depth:
+            raise MdkError(f"moments add over the same samples and min_depth: {self.n_samples} samples {self.names} at {self.min_depth}, and {other.n_samples} {other.names} at {other.min_depth}")
+        if other.n.device != self.n.device:
+            raise MdkError(f"moments add on one device: {self.n.device} and {other.n.device}")
+        sums = [(a + b).contiguous() for a, b in zip((self.n, self.sx, self.sxx, self.sxy), (other.n, other.sx, other.sxx, other.sxy))]
+        most = int(sums[0].max())
+        if most > 1 << 30:
+            raise MdkError(f"{most} sites in all: more than 2^30")
+        return SampleMoments(*sums, *_moments_center(sums), self.min_depth, self.names)
+
+    def _what(self, what):
+        if what not in MOMENTS_WHAT:
+            raise MdkError(f"unknown matrix {what!r}: one of {', '.join(MOMENTS_WHAT)}")
+        return self.n if what == "n" else getattr(self, what)()
+
+    def rows(self, what="correlation"):
+        """(name, value for sample 0, for sample 1, ...) tuples on the host, a tuple per sample: ``what`` is ``"correlation"``,
+        ``"covariance"`` (floats) or ``"n"`` (ints); the names are ``self.names``, or ``s0`` ..."""
+        names = self.names if self.names is not None else tuple(f"s{i}" for i in range(self.n_samples))
+        return [(name,) + tuple(row) for name, row in zip(names, self._what(what).cpu().tolist())]
+
+    def write(self, path, what="correlation"):
+        """A square table as text: one ``#sample NAME ...`` line, then a line per sample, its name and its row of the matrix, tab-separated;
+        doubles as ``%.17g`` (``nan`` where undefined), formatted on the host.  Returns the path."""
+        rows = self.rows(what)
+        with open(path, "w") as f:
+            f.write("\t".join(["#sample"] + [r[0] for r in rows]) + "\n")
+            f.writelines("\t".join([r[0]] + [str(v) if isinstance(v, int) else "%.17g" % v for v in r[1:]]) + "\n" for r in rows)
+        return path
 
 
 # ---- smoothing (include/mdk_smooth.h, csrc/mdk_smooth.hip -> libmdk_smooth.so; the rule is csrc/mdk_smooth_core.h) ----

@@ -91,6 +91,7 @@ extern "C" const char *md_stats_last_error(void) { return g_err; }
 
 struct md_stats : SideHandle<StatsStatus, StatsPinned> {
     int32_t *d_order = nullptr;
+    int32_t mom_shape = 0, mom_chunk = 0, mom_tile = 0, mom_grid = 0;      // md_stats_moments_limits; 0: the default of each
 };
 
 extern "C" int md_stats_open(int device, md_stats **out) {
@@ -162,3 +163,6 @@ extern "C" int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmet
              (long long)(first >> 8));
     return MD_STATS_ERR_ARG;
 }
+
+// the pairwise sample moments: the library's other calls, on the same handle
+#include "mdk_moments.hip"
