@@ -35,6 +35,8 @@ int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmeth, int elem
 
 /* The pairwise sample moments, on the same handle: three more calls, declared and documented in a header of their own */
 #include "mdk_moments.h"
+/* The count profile -- depth and level histograms per sample and group --, on the same handle: two more calls, likewise */
+#include "mdk_profile.h"
 void md_stats_close(md_stats *h);
 const char *md_stats_last_error(void);
 

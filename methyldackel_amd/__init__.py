@@ -1857,6 +1857,31 @@ class Calls(_Columns):
             raise MdkError("merge_context: these rows are merged already (merged is true)")
         return self._merged([getattr(self, name) for name, _ in CALL_COLUMNS], min_depth)
 
+    def profile(self, by="context", min_depth=1, depth_bins=1024, level_bins=20):
+        """The first look at a sample -- methylKit's ``getCoverageStats`` and ``getMethylationStats``: a ``CountProfile`` of these rows as
+        one sample, the counts viewed as ``[1, n]`` and not copied, made on the device by ``count_profile``, which documents the rule.
+        ``by="context"`` groups the rows by their ``context`` column, three groups named CpG, CHG and CHH -- ``profile().rate()[0, 2]``,
+        the methylated fraction of the CHH reads, is the usual estimate of the bisulfite non-conversion rate --; ``by=None`` is one
+        group.  The order of the rows does not matter."""
+        group, n_groups, group_names = _profile_by(by, self.context)
+        return count_profile(self.nmeth.unsqueeze(0), self.nunmeth.unsqueeze(0), group, n_groups, min_depth, depth_bins, level_bins, group_names=group_names)
+
+    def filter_depth(self, lo=10, hi_quantile=0.999, depth_bins=4096):
+        """The rows deep enough to trust and not so deep that they are pile-ups of PCR duplicates or repeats -- the place of methylKit's
+        ``filterByCoverage(lo.count=10, hi.perc=99.9)``: ``select`` of the rows with ``lo <= nmeth + nunmeth <= hi``, where ``hi`` is
+        ``self.profile(min_depth=lo, depth_bins=depth_bins).depth_quantile(hi_quantile)`` of the row's own context -- the percentile
+        of the depths of the rows that pass ``lo``, as ``CountProfile.depth_quantile`` defines it in integers: always a depth some
+        row has, and not R's interpolated type 7 quantile, from which it may differ by the gap between two neighbouring depths.
+        ``hi_quantile=None`` cuts only below.  A percentile at ``depth_bins`` or beyond raises MdkError: raise ``depth_bins``."""
+        if isinstance(lo, bool) or not isinstance(lo, int) or not 1 <= lo < 1 << 26:
+            raise MdkError(f"filter_depth: lo must be an integer within 1 and 2^26 - 1, not {lo!r}")
+        depth = self.nmeth.long() + self.nunmeth.long()
+        keep = depth >= lo
+        if hi_quantile is not None:
+            hi = self.profile("context", lo, depth_bins, 1).depth_quantile(hi_quantile)[0]
+            keep &= depth <= hi[self.context.long()]
+        return self.select(keep)
+
     def regions(self, intervals, contexts=None, strand=None, min_depth=1):
         """These rows added up per interval -- CpG islands, promoters, a BED of candidate DMRs, the tiles every DMR tool starts from --: a
         ``Regions`` with, per interval and in the intervals' own order, ``nsites`` (the rows counted), ``nmeth`` and ``nunmeth`` (int64),
@@ -2282,6 +2307,13 @@ class Cytosines(_Columns):
         interval, at ``min_depth=1`` the number covered; with ``Intervals.windows`` two samples' results line up window for window."""
         return self._regions([self.contig, self.pos - 1, self.pos, self.nmeth, self.nunmeth, self.context, self.strand], intervals, contexts, strand, min_depth)
 
+    def profile(self, by="context", min_depth=1, depth_bins=1024, level_bins=20):
+        """``Calls.profile`` of the report, every cytosine of the reference a cell: bin 0 of ``depth_hist`` holds the cytosines no read
+        covers, ``sites()`` is the cytosines of the reference in the contexts switched on, and ``breadth()`` the share of them
+        covered at ``min_depth``."""
+        group, n_groups, group_names = _profile_by(by, self.context)
+        return count_profile(self.nmeth.unsqueeze(0), self.nunmeth.unsqueeze(0), group, n_groups, min_depth, depth_bins, level_bins, group_names=group_names)
+
     def rows(self):
         """(chrom, pos, "+"/"-", nmeth, nunmeth, "CG"/"CHG"/"CHH", trinucleotide) tuples on the host: the seven fields of a line"""
         cols = [getattr(self, n).cpu().tolist() for n in ("contig", "pos", "strand", "nmeth", "nunmeth", "context")]
@@ -2487,6 +2519,14 @@ class Cohort:
         sample does not hold (``0 0``) is not covered there and takes part in no pair with that sample.
         ``cohort.moments().correlation()`` is the samples' correlation matrix, ``.distance()`` what ``clusterSamples`` clusters on."""
         return sample_moments(self.nmeth, self.nunmeth, min_depth, names=self.names)
+
+    def profile(self, by="context", min_depth=1, depth_bins=1024, level_bins=20):
+        """Every sample's depth and level histograms in one pass -- ``Calls.profile`` for the whole table: a ``CountProfile`` of the two
+        matrices with the table's ``names``, grouped by the ``context`` column (``by=None``: one group), made on the device by
+        ``count_profile``.  Row s is, bit for bit, ``cohort.sample(s).profile(...)``; a site a sample does not hold is a ``0 0`` cell
+        and counts in bin 0 of its ``depth_hist``."""
+        group, n_groups, group_names = _profile_by(by, self.context)
+        return count_profile(self.nmeth, self.nunmeth, group, n_groups, min_depth, depth_bins, level_bins, names=self.names, group_names=group_names)
 
     def smooth(self, half_bases=1000, min_sites=70, kernel="tricube"):
         """Every sample's counts smoothed along the genome, the step between ``unite`` and a test or a plot at low coverage -- what
@@ -3057,6 +3097,250 @@ class SampleMoments:
         with open(path, "w") as f:
             f.write("\t".join(["#sample"] + [r[0] for r in rows]) + "\n")
             f.writelines("\t".join([r[0]] + [str(v) if isinstance(v, int) else "%.17g" % v for v in r[1:]]) + "\n" for r in rows)
+        return path
+
+
+# ---- the count profile (include/mdk_profile.h, csrc/mdk_profile.hip in libmdk_stats.so; the rule is csrc/mdk_profile_core.h) ----
+PROFILE_WHAT = ("summary", "depth", "level")
+PROFILE_MAX_GROUPS, PROFILE_MAX_DEPTH_BINS, PROFILE_MAX_LEVEL_BINS = 4, 4096, 256         # PROF_MAX_* of csrc/mdk_profile_core.h
+PROFILE_SUMMARY_COLUMNS = ("sample", "group", "sites", "covered", "nmeth", "nunmeth", "rate", "mean_depth", "median_depth", "max_depth")
+
+
+def lib_profile():
+    """``lib_stats()``'s library with the profile's two calls bound, at the first call that needs them: the one library and the one
+    handle per device of ``diff_replicates`` and ``sample_moments``"""
+    L = lib_stats()
+    if "md_stats_profile" not in vars(L):
+        L.md_stats_profile_limits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.md_stats_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+    return L
+
+
+def profile_limits(device=0, range_sites=0, band_samples=0, max_workgroups=0):
+    """A test hook (md_stats_profile_limits): the sites of a workgroup's range (a multiple of 64), the samples of a band (1, 2 or 4)
+    and the most workgroups of a launch for the ``count_profile`` calls on ``device`` from now on; 0 is the default of each.  The
+    results do not depend on them."""
+    L = lib_profile()
+    with _side_locks["stats"]:
+        _side_call(L, "stats", "profile_limits", _side_handle(L, "stats", int(device)), int(range_sites), int(band_samples), int(max_workgroups))
+
+
+def _profile_arguments(nmeth, nunmeth, group, n_groups, min_depth, depth_bins, level_bins):
+    """what ``count_profile`` asks of its arguments, checked before the library is touched, the way ``_moments_arguments`` checks: (S, n,
+    the matrices' device)"""
+    import torch
+    what = "count_profile"
+    for name, v, most in (("min_depth", min_depth, (1 << 26) - 1), ("n_groups", n_groups, PROFILE_MAX_GROUPS), ("depth_bins", depth_bins, PROFILE_MAX_DEPTH_BINS),
+                          ("level_bins", level_bins, PROFILE_MAX_LEVEL_BINS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= most:
+            raise MdkError(f"{what}: {name} must be an integer within 1 and {'2^26 - 1' if name == 'min_depth' else most}, not {v!r}")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    if group is not None and (not isinstance(group, torch.Tensor) or group.dim() != 1 or group.dtype != torch.uint8 or int(group.shape[0]) != n):
+        raise MdkError(f"{what}: group must be a uint8 tensor of {n} entries, one per site")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth), ("group", group)):
+        if t is not None and not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous" + ("" if name == "group" else ", sample-major"))
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth), ("group", group)):
+        if t is not None and t.device.type != "cuda":
+            raise MdkError(f"counts are profiled on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    for name, t in (("nunmeth", nunmeth), ("group", group)):
+        if t is not None and t.device != dev:
+            raise MdkError(f"{what}: nmeth is on {dev}, {name} on {t.device}")
+    return S, n, dev
+
+
+def _profile_group_names(group_names, G):
+    """``group_names`` as a tuple of G names, 1 to 255 bytes of 0x21 to 0x7e each, no two alike; None stays None"""
+    if group_names is None:
+        return None
+    try:
+        return _cohort_sample_names(group_names, G)
+    except MdkError as e:
+        raise MdkError("group_names: " + str(e).replace("samples", "groups").replace("sample", "group")) from None
+
+
+def count_profile(nmeth, nunmeth, group=None, n_groups=1, min_depth=1, depth_bins=1024, level_bins=20, names=None, group_names=None):
+    """The first look at a table of counts, before ``unite`` -- what methylKit's ``getCoverageStats``, ``getMethylationStats`` and
+    ``filterByCoverage`` start from: per sample and group of sites the histogram of the depths, the histogram of the methylation
+    levels, the sums and the largest depth, in one pass on the device (csrc/mdk_profile.hip).  ``nmeth`` and ``nunmeth`` are two
+    ``[S, n]`` device tensors of one dtype, int32 or int64, contiguous, row s the counts of sample s.  ``group`` is a contiguous uint8
+    device tensor of n entries, the group of each site, every one below ``n_groups`` (1 to 4) -- a ``context`` column with
+    ``n_groups=3`` --, or None: every site is in group 0.  With d = nmeth + nunmeth of a cell, a ``CountProfile`` of five int64 tensors:
+    ``depth_hist`` ``[S, G, depth_bins + 1]`` counts EVERY cell, d = 0 included, bin b the cells of depth exactly b and the last,
+    the overflow bin, those of ``depth_bins`` (1 to 4096) or more; ``max_depth`` ``[S, G]`` is the largest d.  A cell with d >=
+    ``min_depth`` (1 to 2^26 - 1) is covered: ``level_hist`` ``[S, G, level_bins]`` counts it in bin ``min(level_bins - 1, floor(nmeth *
+    level_bins / d))`` (``level_bins`` 1 to 256: equal bins of the methylated fraction, a cell all methylated in the last), and
+    ``nmeth_sum`` and ``nunmeth_sum`` ``[S, G]`` add its counts.  Exact integers, the same bits on every run, device and blocking of
+    the kernel; the matrices are not changed.  A negative entry, an entry of 2^26 or more and a group of ``n_groups`` or more raise
+    MdkError (rc -3) naming the first such site; so do CPU tensors: there is no CPU path.  Not here: groups by strand or contig, a joint
+    depth x level histogram, a level quantile, ``normalizeCoverage``."""
+    import torch
+    S, n, dev = _profile_arguments(nmeth, nunmeth, group, n_groups, min_depth, depth_bins, level_bins)
+    if names is not None:
+        names = _cohort_sample_names(names, S)
+    group_names = _profile_group_names(group_names, n_groups)
+    L = lib_profile()
+    out = [torch.empty(shape, dtype=torch.int64, device=dev) for shape in ((S, n_groups, depth_bins + 1), (S, n_groups, level_bins), (S, n_groups), (S, n_groups), (S, n_groups))]
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    with _side_locks["stats"]:                               # a handle per device, kept: its calls come from one thread at a time
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "profile", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n,
+                   None if group is None else C.c_void_p(group.data_ptr()), n_groups, min_depth, depth_bins, level_bins, *[C.c_void_p(t.data_ptr()) for t in out])
+    return CountProfile(*out, min_depth, names, group_names)
+
+
+def _profile_by(by, context):
+    """(group, n_groups, group_names) of a ``profile`` method's ``by``"""
+    if by is None:
+        return None, 1, None
+    if by == "context":
+        return context, 3, CONTEXT_FILES
+    raise MdkError(f"profile: by must be \"context\" or None, not {by!r}")
+
+
+class CountProfile:
+    """What ``count_profile`` and the ``profile`` methods return, on the table's device: ``depth_hist`` ``[S, G, depth_bins + 1]``,
+    ``level_hist`` ``[S, G, level_bins]``, ``nmeth_sum``, ``nunmeth_sum`` and ``max_depth`` ``[S, G]`` (int64) as ``count_profile``
+    documents them, ``min_depth``, ``depth_bins``, ``level_bins``, ``n_samples``, ``n_groups``, and ``names`` and ``group_names``,
+    tuples of S sample names and of G group names, or None.  The methods work in torch on the device from these tensors.
+    ``a + b`` is the profile of two disjoint sets of sites -- chromosomes, batches -- of the same samples: the integers add, and
+    ``max_depth`` is the larger."""
+
+    def __init__(self, depth_hist, level_hist, nmeth_sum, nunmeth_sum, max_depth, min_depth=1, names=None, group_names=None):
+        shape = tuple(depth_hist.shape)
+        if len(shape) != 3 or shape[2] < 2 or level_hist.dim() != 3 or tuple(level_hist.shape[:2]) != shape[:2] or level_hist.shape[2] < 1 or \
+                any(tuple(t.shape) != shape[:2] for t in (nmeth_sum, nunmeth_sum, max_depth)):
+            raise MdkError("a CountProfile is made of [S, G, depth_bins + 1], [S, G, level_bins] and three [S, G] tensors")
+        self.depth_hist, self.level_hist, self.nmeth_sum, self.nunmeth_sum, self.max_depth = depth_hist, level_hist, nmeth_sum, nunmeth_sum, max_depth
+        self.min_depth = int(min_depth)
+        self.names = None if names is None else _cohort_sample_names(names, shape[0])
+        self.group_names = _profile_group_names(group_names, shape[1])
+
+    @property
+    def n_samples(self):
+        return int(self.depth_hist.shape[0])
+
+    @property
+    def n_groups(self):
+        return int(self.depth_hist.shape[1])
+
+    @property
+    def depth_bins(self):
+        return int(self.depth_hist.shape[2]) - 1
+
+    @property
+    def level_bins(self):
+        return int(self.level_hist.shape[2])
+
+    def sites(self):
+        """int64 ``[S, G]``: the cells counted, covered or not -- for a ``Cytosines`` the cytosines of the reference"""
+        return self.depth_hist.sum(2)
+
+    def covered(self):
+        """int64 ``[S, G]``: the cells with a depth of ``min_depth`` or more"""
+        return self.level_hist.sum(2)
+
+    def breadth(self):
+        """float64 ``[S, G]``: ``covered / sites``, the correctly rounded quotient; NaN where there is no site"""
+        return self.covered().double() / self.sites().double()
+
+    def mean_depth(self):
+        """float64 ``[S, G]``: the mean depth of the covered cells, ``(nmeth_sum + nunmeth_sum) / covered`` -- the correctly rounded
+        quotient while the sum is below 2^53; NaN where nothing is covered"""
+        return (self.nmeth_sum + self.nunmeth_sum).double() / self.covered().double()
+
+    def rate(self):
+        """float64 ``[S, G]``: the methylated fraction of the covered cells' reads, ``nmeth_sum / (nmeth_sum + nunmeth_sum)`` -- the
+        correctly rounded quotient while the sums are below 2^53; NaN where that is 0.  In CHH this is the usual estimate of the
+        bisulfite non-conversion rate."""
+        return self.nmeth_sum.double() / (self.nmeth_sum + self.nunmeth_sum).double()
+
+    def _label(self, s, g):
+        return (self.names[s] if self.names is not None else f"s{s}"), (self.group_names[g] if self.group_names is not None else "all" if self.n_groups == 1 else f"g{g}")
+
+    def depth_quantile(self, q):
+        """int64 ``[S, G]``: a percentile of the covered cells' depths, read from ``depth_hist`` without a sort and defined in integers.
+        With N the covered count and k = max(1, ceil(Fraction(q) * N)) -- Fraction(q) the exact value of the float ``q``, within [0,
+        1] --, the smallest depth v such that at least k covered cells have a depth of v or less, counted from bin ``min_depth`` up;
+        -1 where N is 0.  So q = 0 is the smallest covered depth, q = 1 the largest, and the result is always a depth some cell has:
+        the rule is not R's interpolated type 7.  If a result would lie in the overflow bin -- with ``min_depth >= depth_bins`` every
+        covered cell does -- MdkError names the sample, the group and its ``max_depth``: raise ``depth_bins``."""
+        import math
+        from fractions import Fraction
+        import torch
+        if isinstance(q, bool) or not isinstance(q, (int, float)) or not 0 <= q <= 1:        # (a NaN is in no range)
+            raise MdkError(f"depth_quantile: q must be a number within 0 and 1, not {q!r}")
+        fq, B = Fraction(q), self.depth_bins
+        hist = self.depth_hist.clone()
+        hist[:, :, :min(self.min_depth, B)] = 0                                            # (at min_depth >= B every covered cell is in bin B)
+        N = hist.sum(2)
+        k = torch.tensor([[max(1, math.ceil(fq * v)) for v in row] for row in N.cpu().tolist()], dtype=torch.int64, device=N.device).reshape(N.shape)
+        v = (hist.cumsum(2) < k.unsqueeze(2)).sum(2)                                       # the first bin at which the running count reaches k
+        over = ((N > 0) & (v >= B)).nonzero()
+        if over.shape[0]:
+            s, g = (int(x) for x in over[0].cpu().tolist())
+            name, group = self._label(s, g)
+            raise MdkError(f"depth_quantile({q!r}): for sample {name}, group {group}, it lies in the overflow bin, depth {B} or more (max_depth {int(self.max_depth[s, g])}): raise depth_bins")
+        return torch.where(N > 0, v, torch.full_like(v, -1))
+
+    def median_depth(self):
+        """``depth_quantile(0.5)``"""
+        return self.depth_quantile(0.5)
+
+    def __add__(self, other):
+        import torch
+        if not isinstance(other, CountProfile):
+            return NotImplemented
+        mine = (tuple(self.depth_hist.shape), tuple(self.level_hist.shape), self.min_depth, self.names, self.group_names)
+        theirs = (tuple(other.depth_hist.shape), tuple(other.level_hist.shape), other.min_depth, other.names, other.group_names)
+        if mine != theirs:
+            raise MdkError(f"profiles add over the same samples, groups, bins and min_depth: {mine}, and {theirs}")
+        if other.depth_hist.device != self.depth_hist.device:
+            raise MdkError(f"profiles add on one device: {self.depth_hist.device} and {other.depth_hist.device}")
+        return CountProfile(self.depth_hist + other.depth_hist, self.level_hist + other.level_hist, self.nmeth_sum + other.nmeth_sum, self.nunmeth_sum + other.nunmeth_sum,
+                            torch.maximum(self.max_depth, other.max_depth), self.min_depth, self.names, self.group_names)
+
+    def rows(self, what="summary"):
+        """Tuples on the host, sample-major, then by group.  ``what="summary"``, one per (sample, group): (sample, group, sites, covered,
+        nmeth_sum, nunmeth_sum, rate, mean_depth, median_depth, max_depth) -- ints but for ``rate`` and ``mean_depth``, floats that are
+        NaN where nothing is covered; ``median_depth`` is -1 there, and raises as ``depth_quantile`` does where it lies in the overflow
+        bin.  ``"depth"``, one per bin: (sample, group, depth, count), the last bin's ``depth`` being ``depth_bins``: that or more.
+        ``"level"``, one per bin: (sample, group, bin, lower, upper, count) with the bin's bounds ``bin / level_bins`` and ``(bin + 1) /
+        level_bins`` as floats.  The names are ``names`` and ``group_names``, or ``s0`` ... and ``g0`` ... (``all`` for one group)."""
+        if what not in PROFILE_WHAT:
+            raise MdkError(f"unknown table {what!r}: one of {', '.join(PROFILE_WHAT)}")
+        S, G = self.n_samples, self.n_groups
+        cells = [(s, g) + self._label(s, g) for s in range(S) for g in range(G)]
+        if what == "summary":
+            cols = [t.cpu().tolist() for t in (self.sites(), self.covered(), self.nmeth_sum, self.nunmeth_sum, self.rate(), self.mean_depth(), self.median_depth(), self.max_depth)]
+            return [(name, group) + tuple(c[s][g] for c in cols) for s, g, name, group in cells]
+        if what == "depth":
+            hist = self.depth_hist.cpu().tolist()
+            return [(name, group, b, v) for s, g, name, group in cells for b, v in enumerate(hist[s][g])]
+        hist, L = self.level_hist.cpu().tolist(), self.level_bins
+        return [(name, group, l, l / L, (l + 1) / L, v) for s, g, name, group in cells for l, v in enumerate(hist[s][g])]
+
+    def write(self, path, what="summary"):
+        """A small table as text, formatted on the host: a first line ``#count_profile WHAT min_depth=M depth_bins=B level_bins=L``, a
+        second of the column names -- ``#sample group sites covered nmeth nunmeth rate mean_depth median_depth max_depth``, ``#sample
+        group depth count`` or ``#sample group bin lower upper count`` --, then ``rows(what)``, a line each; all tab-separated, ints
+        as they are, doubles as ``%.17g`` (``nan`` where undefined).  Returns the path."""
+        rows = self.rows(what)
+        columns = PROFILE_SUMMARY_COLUMNS if what == "summary" else ("sample", "group", "depth", "count") if what == "depth" else ("sample", "group", "bin", "lower", "upper", "count")
+        with open(path, "w") as f:
+            f.write(f"#count_profile\t{what}\tmin_depth={self.min_depth}\tdepth_bins={self.depth_bins}\tlevel_bins={self.level_bins}\n")
+            f.write("#" + "\t".join(columns) + "\n")
+            f.writelines("\t".join("%.17g" % v if isinstance(v, float) else str(v) for v in r) + "\n" for r in rows)
         return path
 
 

@@ -92,6 +92,7 @@ extern "C" const char *md_stats_last_error(void) { return g_err; }
 struct md_stats : SideHandle<StatsStatus, StatsPinned> {
     int32_t *d_order = nullptr;
     int32_t mom_shape = 0, mom_chunk = 0, mom_tile = 0, mom_grid = 0;      // md_stats_moments_limits; 0: the default of each
+    int32_t prof_range = 0, prof_band = 0, prof_grid = 0;                  // md_stats_profile_limits; likewise
 };
 
 extern "C" int md_stats_open(int device, md_stats **out) {
@@ -166,3 +167,5 @@ extern "C" int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmet
 
 // the pairwise sample moments: the library's other calls, on the same handle
 #include "mdk_moments.hip"
+// the count profile: likewise
+#include "mdk_profile.hip"
