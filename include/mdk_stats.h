@@ -37,6 +37,8 @@ int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmeth, int elem
 #include "mdk_moments.h"
 /* The count profile -- depth and level histograms per sample and group --, on the same handle: two more calls, likewise */
 #include "mdk_profile.h"
+/* Three or more groups of replicate samples -- the F test with groups - 1 numerator degrees of freedom --, on the same handle: one more call, likewise */
+#include "mdk_gdiff.h"
 void md_stats_close(md_stats *h);
 const char *md_stats_last_error(void);
 

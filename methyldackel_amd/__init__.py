@@ -2513,6 +2513,19 @@ class Cohort:
         cols.update(zip((name for name, _ in REPLICATE_RESULT_COLUMNS), out))
         return ReplicateDiff(self.contigs, cols, merged=self.merged)
 
+    def diff_groups(self, groups, min_dispersion=1.0, names=None):
+        """``diff_replicates`` for THREE OR MORE groups of replicates -- a time course, several tissues, a dose series: the omnibus F
+        test of ``diff_groups`` on the table's matrices, one pass whatever the number of groups.  ``groups`` is a sequence of
+        sequences of sample indices (disjoint, none empty; the other samples are not read), ``names`` the groups' names for ``write``
+        (``g0``, ``g1``, ... by default).  A ``GroupDiff`` with this table's site columns (the same tensors), the groups' pooled counts
+        as two ``[G, n]`` matrices, ``meth_diff`` between the most and the least methylated group, which two these are, and the
+        test's ``pvalue``, ``df``, ``df_groups``, ``dispersion`` and ``statistic``.  ``GroupDiff.contrast(i, j)`` is the ``Diff`` of
+        two of the groups, one call away.  With one sample a group every site has p 1.0 and df 0."""
+        out = diff_groups(self.nmeth, self.nunmeth, groups, min_dispersion=min_dispersion)
+        cols = {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}
+        cols.update(zip((name for name, _ in GROUP_RESULT_COLUMNS), out[2:]))
+        return GroupDiff(self.contigs, cols, out[0], out[1], merged=self.merged, names=names, _text=self._text)
+
     def moments(self, min_depth=1):
         """How alike the table's samples are, the first look after ``unite`` -- methylKit's ``getCorrelation``: a ``SampleMoments`` of
         the two matrices with the table's ``names``, made on the device by ``sample_moments``, which documents the rule.  A site a
@@ -2858,8 +2871,8 @@ def diff_counts(nmeth, nunmeth, a, b, _text=None):
     coverage, 0.0 where it would be below about 1e-280).  The p-value is made of IEEE multiplications, divisions and additions in a
     fixed order (csrc/mdk_diff_core.h): the same bits on every run and every device, exact to about (4 * support + 8) * 2^-53.  A
     negative entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do
-    CPU tensors: there is no CPU path.  Not here: one-sided tests, more than two groups; the over-dispersion between replicates
-    is ``diff_replicates``'s."""
+    CPU tensors: there is no CPU path.  Not here: one-sided tests; more than two groups are ``diff_groups``', the over-dispersion
+    between replicates is ``diff_replicates``'s."""
     import torch
     S, n, marks, dev = _diff_arguments("diff_counts", nmeth, nunmeth, a, b)
     L = _text_lib()
@@ -2908,7 +2921,8 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     (csrc/mdk_qdiff_core.h): the same bits on every run and every device; the p-value's relative error is bounded by (4 steps + 12 nu +
     32) * 2^-53 from 1e-280 up, and it is 0.0 below that.  ``min_dispersion`` is a finite float within [2^-55, 2^800].  A negative
     entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do CPU
-    tensors: there is no CPU path.  Not here: covariates, more than two groups, one-sided tests, the deviance statistic."""
+    tensors: there is no CPU path.  Not here: covariates, one-sided tests, the deviance statistic; more than two groups are
+    ``diff_groups``'."""
     import torch
     if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
         raise MdkError(f"diff_replicates: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
@@ -2923,6 +2937,112 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     with _side_locks["stats"]:                               # a handle per device, kept: its calls come from one thread at a time
         h = _side_handle(L, "stats", dev.index or 0)
         _side_call(L, "stats", "qdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(groups[0]), len(groups[1]),
+                   float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
+    return tuple(out)
+
+
+# ---- three or more groups of replicates (include/mdk_gdiff.h, csrc/mdk_gdiff.hip in libmdk_stats.so; the rule is csrc/mdk_gdiff_core.h) ----
+GROUP_RESULT_COLUMNS = (("meth_diff", "float64"), ("group_lo", "int32"), ("group_hi", "int32"), ("pvalue", "float64"), ("df", "int32"), ("df_groups", "int32"),
+                        ("dispersion", "float64"), ("statistic", "float64"))
+
+
+def lib_groups():
+    """``lib_stats()``'s library with ``diff_groups``' call bound, at the first call that needs it: the one library and the one handle
+    per device of ``diff_replicates``, ``sample_moments`` and ``count_profile``"""
+    L = lib_stats()
+    if "md_stats_gdiff" not in vars(L):
+        L.md_stats_gdiff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_double] + [C.c_void_p] * 11
+    return L
+
+
+def _group_arguments(what, nmeth, nunmeth, groups):
+    """what ``diff_groups`` asks of its arguments, checked before the library is touched, in ``_diff_arguments``' words: (S, n, the groups
+    as lists of row indices, each ascending -- the rule's visiting order --, the matrices' device)"""
+    import torch
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    if isinstance(groups, (str, bytes)) or not hasattr(groups, "__iter__"):
+        raise MdkError(f"{what}: groups must be a sequence of 2 to {S} sequences of sample indices, not {groups!r}")
+    groups = list(groups)
+    if not 2 <= len(groups) <= S:
+        raise MdkError(f"{what}: {len(groups)} groups: 2 to {S}, the samples of the matrices")
+    marks, out = [-1] * S, []
+    for g, group in enumerate(groups):
+        if isinstance(group, (str, bytes)) or not (hasattr(group, "__iter__") or hasattr(group, "__index__")):
+            raise MdkError(f"{what}: group {g} must be a sequence of sample indices, not {group!r}")
+        group = [group] if hasattr(group, "__index__") and not hasattr(group, "__iter__") else list(group)
+        if not group:
+            raise MdkError(f"{what}: group {g} is empty")
+        for i in group:
+            if isinstance(i, bool) or not hasattr(i, "__index__") or not 0 <= int(i) < S:
+                raise MdkError(f"{what}: group {g} names sample {i!r}: the matrices hold samples 0 to {S - 1}")
+            i = int(i)
+            if marks[i] not in (-1, g):
+                raise MdkError(f"{what}: sample {i} is in both groups {marks[i]} and {g}")
+            marks[i] = g
+        out.append([s for s in range(S) if marks[s] == g])
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous, sample-major")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if t.device.type != "cuda":
+            raise MdkError(f"groups are compared on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    if nunmeth.device != dev:
+        raise MdkError(f"{what}: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    return S, n, out, dev
+
+
+def diff_groups(nmeth, nunmeth, groups, min_dispersion=1.0, steps=False):
+    """THREE OR MORE groups of replicate samples compared site by site on the device (csrc/mdk_gdiff.hip): the omnibus test "some group
+    differs" -- a time course, several tissues, a dose series, control / het / hom --, where ``diff_replicates`` has two groups.
+    ``nmeth`` and ``nunmeth`` are ``diff_counts``' matrices, checked as it checks them -- a ``Cohort``'s, or a ``CohortRegions``' --;
+    ``groups`` is a sequence of 2 to S sequences of row indices, disjoint, none empty; rows in none are not read.  Per site a sample
+    with ``nmeth + nunmeth == 0`` is not covered and is left out, and so is a group without a covered sample; with g covered groups
+    and k covered samples in them, q = g - 1 and nu = k - g.  The statistic is Pearson's chi-square of the pooled g x 2 table over q
+    times the dispersion -- ``diff_replicates``' estimate, Pearson's residuals of the covered samples around their group's pooled
+    fraction, squared, added and divided by nu, and ``min_dispersion`` where that is smaller --, and the p-value is P(F(q, nu) >
+    statistic): methylKit's ``calculateDiffMeth`` for several treatment levels with ``overdispersion="MN", test="F"``, the score
+    statistic in the place of the deviance.  Returns ``nmeth`` and ``nunmeth`` (int64 ``[G, n]``: the groups' entries added),
+    ``meth_diff`` (float64: the most methylated covered group's percentage less the least methylated one's, never negative, which is
+    what methylKit reports for several groups), ``group_lo`` and ``group_hi`` (int32: these two groups, a tie to the lower index; -1
+    where no group is covered), ``pvalue`` (float64), ``df`` (int32: nu, 0 below 1), ``df_groups`` (int32: q), ``dispersion`` and
+    ``statistic`` (float64); with ``steps=True`` one more, uint32: the terms the tail's series took.  A site with nothing to test --
+    fewer than two covered groups, nu < 1 (one sample a group: a design without replicates), nothing or everything methylated -- has
+    pvalue 1.0, dispersion 1.0 and statistic 0.0.  A site with two covered groups has ``diff_replicates``' pvalue, df, dispersion and
+    statistic of them bit for bit, and so has every site of a call with two groups.  All of it is IEEE multiplications, divisions
+    and additions in one order (csrc/mdk_gdiff_core.h): the same bits on every run and every device; the p-value's relative error is
+    bounded by (4 steps + 12 (nu + q) + 32) * 2^-53 from 1e-280 up, and it may be 0.0 below that.  Refusals are ``diff_replicates``':
+    a negative entry, an entry of 2^26 or more and a pooled margin -- a group's depth, the methylated or the unmethylated of all
+    groups -- of 2^26 or more raise MdkError (rc -3) naming the first such site; so do CPU tensors: there is no CPU path.  Not here:
+    covariates, the deviance statistic, one-sided or trend tests, a chi-square p-value for designs without replicates."""
+    import torch
+    if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
+        raise MdkError(f"diff_groups: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
+    S, n, groups, dev = _group_arguments("diff_groups", nmeth, nunmeth, groups)
+    G = len(groups)
+    flat = [s for group in groups for s in group]
+    ends, at = [], 0
+    for group in groups:
+        at += len(group)
+        ends.append(at)
+    order, group_end = (C.c_int32 * len(flat))(*flat), (C.c_int32 * G)(*ends)
+    L = lib_groups()
+    out = [torch.empty((G, n), dtype=torch.int64, device=dev) for _ in range(2)] + [torch.empty(n, dtype=getattr(torch, dt), device=dev) for _, dt in GROUP_RESULT_COLUMNS]
+    if steps:
+        out.append(torch.empty(n, dtype=torch.uint32, device=dev))
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    with _side_locks["stats"]:                               # the handle of diff_replicates: its calls come from one thread at a time
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "gdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, group_end, G,
                    float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
     return tuple(out)
 
@@ -3734,6 +3854,76 @@ class ReplicateDiff(Diff):
         with %.17g, which reads back to the same bits.  Returns the path."""
         with open(path, "w") as f:
             f.writelines("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\t%d\t%.17g\t%.17g\n" % r for r in self.rows())
+        return path
+
+
+class GroupDiff:
+    """What ``Cohort.diff_groups`` returns, one entry per site of the cohort, on its device: ``contig``, ``start``, ``end`` (int32),
+    ``context`` (uint8) and ``strand`` (int8) are the cohort's own tensors; ``nmeth`` and ``nunmeth`` (int64 ``[G, n]``) the groups'
+    pooled counts, row g group g's; ``meth_diff`` (float64) the most methylated covered group's percentage less the least methylated
+    one's, ``group_lo`` and ``group_hi`` (int32) these two groups; ``pvalue`` (float64) the quasi-binomial F test's, ``df`` and
+    ``df_groups`` (int32) its degrees of freedom, ``dispersion`` and ``statistic`` (float64).  ``contigs`` and ``merged`` are the
+    cohort's, ``n_groups`` is G and ``names`` the groups' names.  It is not a ``Diff``: more than two groups have no direction to join
+    regions on -- ``contrast(i, j)`` gives the ``Diff`` of a pair, with its direction, Fisher's p and ``dmrs``."""
+    COLUMNS = DIFF_SITE_COLUMNS + GROUP_RESULT_COLUMNS
+
+    def __init__(self, contigs, columns, nmeth, nunmeth, merged=False, names=None, _text=None):
+        self.contigs = contigs
+        for name, _ in self.COLUMNS:
+            setattr(self, name, columns[name])
+        self.nmeth, self.nunmeth = nmeth, nunmeth
+        self.merged = bool(merged)
+        G = int(nmeth.shape[0])
+        self.names = _cohort_sample_names(names if names is not None else [f"g{g}" for g in range(G)], G)
+        self._text = _text
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    @property
+    def n_groups(self):
+        return int(self.nmeth.shape[0])
+
+    def qvalue(self):
+        """the omnibus p-values adjusted as Benjamini and Hochberg do, over the sites of this table: ``Diff.qvalue``'s rule"""
+        return _benjamini_hochberg(self.pvalue)
+
+    def select(self, index):
+        """a copy with the sites ``column[index]`` (a boolean mask, an index tensor, a slice): of every column, and of the two matrices
+        along their site axis"""
+        cols = {name: getattr(self, name)[index].contiguous() for name, _ in self.COLUMNS}
+        return GroupDiff(self.contigs, cols, self.nmeth[:, index].contiguous(), self.nunmeth[:, index].contiguous(), self.merged, self.names, self._text)
+
+    def contrast(self, i, j):
+        """Groups ``i`` and ``j`` compared as ``Cohort.diff`` compares them, from their pooled counts: a ``Diff`` with this table's site
+        columns (the same tensors), group i as a and group j as b -- ``meth_diff`` j minus i, ``pvalue`` Fisher's exact test of the
+        pooled 2 x 2 table --, made on the device by ``diff_counts(self.nmeth, self.nunmeth, [i], [j])``.  So a pair's direction and
+        ``dmrs`` are one call away: ``g.contrast(0, 2).dmrs(g.qvalue() < 0.01)``."""
+        out = diff_counts(self.nmeth, self.nunmeth, [i], [j], _text=self._text)
+        cols = {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}
+        cols.update(zip((name for name, _ in DIFF_RESULT_COLUMNS), out))
+        return Diff(self.contigs, cols, merged=self.merged)
+
+    def rows(self):
+        """(chrom, start, end, context, strand, (nmeth, nunmeth) of group 0, of group 1, ..., meth_diff, group_lo, group_hi, pvalue, df,
+        df_groups, dispersion, statistic) tuples on the host"""
+        site = [getattr(self, n).cpu().tolist() for n, _ in DIFF_SITE_COLUMNS]
+        result = [getattr(self, n).cpu().tolist() for n, _ in GROUP_RESULT_COLUMNS]
+        m, u = self.nmeth.t().cpu().tolist(), self.nunmeth.t().cpu().tolist()
+        return [(self.contigs[s[0]],) + s[1:] + tuple(zip(mm, uu)) + r for s, mm, uu, r in zip(zip(*site), m, u, zip(*result))]
+
+    def write(self, path):
+        """a header line -- ``#chrom start end context strand``, then ``NAME.nmeth NAME.nunmeth`` for every group, then the eight result
+        columns' names --, then a line per site, tab-separated, the contig by its name; formatted on the host, the four doubles with
+        %.17g, which reads back to the same bits.  Returns the path."""
+        head = ["#chrom", "start", "end", "context", "strand"] + [f"{v}.{w}" for v in self.names for w in ("nmeth", "nunmeth")] + [n for n, _ in GROUP_RESULT_COLUMNS]
+        G = self.n_groups
+        with open(path, "w") as f:
+            f.write("\t".join(head) + "\n")
+            for r in self.rows():
+                cells = ["%s" % r[0]] + ["%d" % v for v in r[1:5]] + ["%d" % v for pair in r[5:5 + G] for v in pair]
+                d, lo, hi, p, df, dfg, phi, stat = r[5 + G:]
+                f.write("\t".join(cells + ["%.17g" % d, "%d" % lo, "%d" % hi, "%.17g" % p, "%d" % df, "%d" % dfg, "%.17g" % phi, "%.17g" % stat]) + "\n")
         return path
 
 

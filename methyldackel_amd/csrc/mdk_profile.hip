@@ -251,3 +251,7 @@ extern "C" int md_stats_profile(md_stats *h, const void *nmeth, const void *nunm
     else snprintf(g_err, sizeof g_err, "%s: %s (site %lld)", what, bit == MOM_E_NEGATIVE ? "a count is negative" : "a count is 2^26 or more", (long long)(first >> 8));
     return MD_STATS_ERR_ARG;
 }
+
+// three or more groups of replicates: one more call and one more kernel of the library, on the same handle (this file is the last
+// that mdk_qdiff.hip includes, and it hands on to the next)
+#include "mdk_gdiff.hip"

@@ -29,7 +29,7 @@
 #define QDIFF_WG 256
 
 struct StatsStatus { unsigned long long first; };              // the smallest (site << 8 | refusal's bit number); all ones: none
-struct StatsPinned { StatsStatus st; int32_t order[DIFF_MAX_SAMPLES]; };
+struct StatsPinned { StatsStatus st; int32_t order[DIFF_MAX_SAMPLES]; int32_t group_end[DIFF_MAX_SAMPLES]; };          // (group_end: md_stats_gdiff's)
 
 struct KQdiff {
     const void *m, *u; const int32_t *order; int32_t n_a, n_b; int64_t n; double min_dispersion;
@@ -90,18 +90,21 @@ __global__ __launch_bounds__(QDIFF_WG) void k_qdiff(const KQdiff K) {
 extern "C" const char *md_stats_last_error(void) { return g_err; }
 
 struct md_stats : SideHandle<StatsStatus, StatsPinned> {
-    int32_t *d_order = nullptr;
+    int32_t *d_order = nullptr, *d_group_end = nullptr;                      // (d_group_end: md_stats_gdiff's, the groups' ends in d_order)
     int32_t mom_shape = 0, mom_chunk = 0, mom_tile = 0, mom_grid = 0;      // md_stats_moments_limits; 0: the default of each
     int32_t prof_range = 0, prof_band = 0, prof_grid = 0;                  // md_stats_profile_limits; likewise
 };
 
 extern "C" int md_stats_open(int device, md_stats **out) {
-    return side_open(device, out, "md_stats_open", md_stats_close, [](md_stats *h) { return hipMalloc((void **)&h->d_order, DIFF_MAX_SAMPLES * sizeof(int32_t)); });
+    return side_open(device, out, "md_stats_open", md_stats_close, [](md_stats *h) {
+        const hipError_t e = hipMalloc((void **)&h->d_order, DIFF_MAX_SAMPLES * sizeof(int32_t));
+        return e != hipSuccess ? e : hipMalloc((void **)&h->d_group_end, DIFF_MAX_SAMPLES * sizeof(int32_t));
+    });
 }
 
 extern "C" void md_stats_close(md_stats *h) {
     if(!h) return;
-    h->close(); (void)hipFree(h->d_order);
+    h->close(); (void)hipFree(h->d_order); (void)hipFree(h->d_group_end);
     delete h;
 }
 
