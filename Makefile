@@ -34,8 +34,8 @@ $(B)/libmdk_$(1).so: $(CSRC)/$(2) $(CSRC)/mdk_side.hpp $(3)
 endef
 # the tabix index (the first index call)
 $(eval $(call side_lib,index,mdk_tabix.hip,$(CSRC)/mdk_tabix_core.h $(CSRC)/mdk_parse_core.h include/mdk_index.h))
-# the replicates' F test of two and of more groups, the pairwise sample moments and the count profile (the first diff_replicates / diff_groups / sample_moments / count_profile call)
-$(eval $(call side_lib,stats,mdk_qdiff.hip,$(CSRC)/mdk_qdiff_core.h $(CSRC)/mdk_diff_core.h $(CSRC)/mdk_moments.hip $(CSRC)/mdk_moments_core.h $(CSRC)/mdk_profile.hip $(CSRC)/mdk_profile_core.h $(CSRC)/mdk_gdiff.hip $(CSRC)/mdk_gdiff_core.h include/mdk_stats.h include/mdk_moments.h include/mdk_profile.h include/mdk_gdiff.h))
+# the replicates' F test of two groups, of more groups and of a design's columns, the pairwise sample moments and the count profile (the first diff_replicates / diff_groups / diff_model / sample_moments / count_profile call)
+$(eval $(call side_lib,stats,mdk_qdiff.hip,$(CSRC)/mdk_qdiff_core.h $(CSRC)/mdk_diff_core.h $(CSRC)/mdk_moments.hip $(CSRC)/mdk_moments_core.h $(CSRC)/mdk_profile.hip $(CSRC)/mdk_profile_core.h $(CSRC)/mdk_gdiff.hip $(CSRC)/mdk_gdiff_core.h $(CSRC)/mdk_mdiff.hip $(CSRC)/mdk_mdiff_core.h include/mdk_stats.h include/mdk_moments.h include/mdk_profile.h include/mdk_gdiff.h include/mdk_mdiff.h))
 # the bigWig track (the first render_bigwig / write_bigwig call): mdk_bigwig_core.h's BW_NO_CONTRACT keeps the products unfused, and the file's bytes are the host build's
 $(eval $(call side_lib,track,mdk_bigwig.hip,$(CSRC)/mdk_bigwig_core.h $(CSRC)/mdk_deflate_core.h include/mdk_track.h))
 # smoothing (the first smooth call): mdk_smooth_core.h's MDK_SMO_NO_CONTRACT keeps the products unfused
@@ -43,7 +43,7 @@ $(eval $(call side_lib,smooth,mdk_smooth.hip,$(CSRC)/mdk_smooth_core.h include/m
 # the united table as text and back, and its sums over intervals (the first Cohort.write / render / read / regions call)
 $(eval $(call side_lib,cohort,mdk_cohort.hip,$(CSRC)/mdk_cohort_core.h $(CSRC)/mdk_text_core.h $(CSRC)/mdk_parse_core.h $(CSRC)/mdk_cregion.hip $(CSRC)/mdk_cregion_core.h $(CSRC)/mdk_region_core.h include/mdk_cohort.h))
 
-tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/gdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/moments_emu tools/_build/profile_emu tools/_build/cohort_emu tools/_build/cregion_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/moments_bench tools/_build/profile_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
+tools: tools/_build/mdk_synth tools/_build/mdk_replicate tools/_build/fasta_probe tools/_build/mdk_calib tools/_build/inflate_emu tools/_build/text_emu tools/_build/merge_emu tools/_build/parse_emu tools/_build/region_emu tools/_build/deflate_emu tools/_build/bigwig_emu tools/_build/tabix_emu tools/_build/unite_emu tools/_build/diff_emu tools/_build/qdiff_emu tools/_build/gdiff_emu tools/_build/mdiff_emu tools/_build/dmr_emu tools/_build/smooth_emu tools/_build/moments_emu tools/_build/profile_emu tools/_build/cohort_emu tools/_build/cregion_emu tools/_build/diff_bench tools/_build/smooth_bench tools/_build/moments_bench tools/_build/profile_bench tools/_build/piece_bench tools/_build/pin_probe tools/_build/feed_harness tools/_build/libmdk_piece_standin.so tools/_build/libmdk_dev_standin.so
 tools/_build/libmdk_piece_standin.so: tools/piece_standin.c include/mdk_hip.h
 	@mkdir -p tools/_build
 	$(CC) -O2 -g -Wall -shared -fPIC -Iinclude -o $@ tools/piece_standin.c -lz
@@ -92,6 +92,9 @@ tools/_build/qdiff_emu: tools/qdiff_emu.cpp methyldackel_amd/csrc/mdk_qdiff_core
 tools/_build/gdiff_emu: tools/gdiff_emu.cpp methyldackel_amd/csrc/mdk_gdiff_core.h methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -ffp-contract=off -o $@ tools/gdiff_emu.cpp -Imethyldackel_amd/csrc
+tools/_build/mdiff_emu: tools/mdiff_emu.cpp methyldackel_amd/csrc/mdk_mdiff_core.h methyldackel_amd/csrc/mdk_gdiff_core.h methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h
+	@mkdir -p tools/_build
+	g++ -O2 -Wall -std=c++17 -ffp-contract=off -o $@ tools/mdiff_emu.cpp -Imethyldackel_amd/csrc
 tools/_build/dmr_emu: tools/dmr_emu.cpp methyldackel_amd/csrc/mdk_dmr_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_region_core.h
 	@mkdir -p tools/_build
 	g++ -O2 -Wall -ffp-contract=off -o $@ tools/dmr_emu.cpp -Imethyldackel_amd/csrc
@@ -113,10 +116,10 @@ tools/_build/cregion_emu: tools/cregion_emu.cpp methyldackel_amd/csrc/mdk_cregio
 tools/_build/smooth_bench: tools/smooth_bench.hip methyldackel_amd/csrc/mdk_smooth.hip methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_smooth_core.h include/mdk_smooth.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/smooth_bench.hip
-tools/_build/moments_bench: tools/moments_bench.hip methyldackel_amd/csrc/mdk_qdiff.hip methyldackel_amd/csrc/mdk_gdiff.hip methyldackel_amd/csrc/mdk_gdiff_core.h include/mdk_gdiff.h methyldackel_amd/csrc/mdk_moments.hip methyldackel_amd/csrc/mdk_profile.hip methyldackel_amd/csrc/mdk_profile_core.h include/mdk_profile.h methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_moments_core.h include/mdk_stats.h include/mdk_moments.h
+tools/_build/moments_bench: tools/moments_bench.hip methyldackel_amd/csrc/mdk_qdiff.hip methyldackel_amd/csrc/mdk_gdiff.hip methyldackel_amd/csrc/mdk_gdiff_core.h include/mdk_gdiff.h methyldackel_amd/csrc/mdk_mdiff.hip methyldackel_amd/csrc/mdk_mdiff_core.h include/mdk_mdiff.h methyldackel_amd/csrc/mdk_moments.hip methyldackel_amd/csrc/mdk_profile.hip methyldackel_amd/csrc/mdk_profile_core.h include/mdk_profile.h methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_moments_core.h include/mdk_stats.h include/mdk_moments.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/moments_bench.hip
-tools/_build/profile_bench: tools/profile_bench.hip methyldackel_amd/csrc/mdk_qdiff.hip methyldackel_amd/csrc/mdk_gdiff.hip methyldackel_amd/csrc/mdk_gdiff_core.h include/mdk_gdiff.h methyldackel_amd/csrc/mdk_moments.hip methyldackel_amd/csrc/mdk_profile.hip methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_moments_core.h methyldackel_amd/csrc/mdk_profile_core.h include/mdk_stats.h include/mdk_moments.h include/mdk_profile.h
+tools/_build/profile_bench: tools/profile_bench.hip methyldackel_amd/csrc/mdk_qdiff.hip methyldackel_amd/csrc/mdk_gdiff.hip methyldackel_amd/csrc/mdk_gdiff_core.h include/mdk_gdiff.h methyldackel_amd/csrc/mdk_mdiff.hip methyldackel_amd/csrc/mdk_mdiff_core.h include/mdk_mdiff.h methyldackel_amd/csrc/mdk_moments.hip methyldackel_amd/csrc/mdk_profile.hip methyldackel_amd/csrc/mdk_side.hpp methyldackel_amd/csrc/mdk_qdiff_core.h methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_moments_core.h methyldackel_amd/csrc/mdk_profile_core.h include/mdk_stats.h include/mdk_moments.h include/mdk_profile.h
 	@mkdir -p tools/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -Imethyldackel_amd/csrc -o $@ tools/profile_bench.hip
 tools/_build/diff_bench: tools/diff_bench.hip methyldackel_amd/csrc/mdk_diff.hip methyldackel_amd/csrc/mdk_diff_core.h methyldackel_amd/csrc/mdk_text_internal.hpp methyldackel_amd/csrc/mdk_hip_internal.hpp include/mdk_hip.h

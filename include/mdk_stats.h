@@ -39,6 +39,8 @@ int md_stats_qdiff(md_stats *h, const void *nmeth, const void *nunmeth, int elem
 #include "mdk_profile.h"
 /* Three or more groups of replicate samples -- the F test with groups - 1 numerator degrees of freedom --, on the same handle: one more call, likewise */
 #include "mdk_gdiff.h"
+/* A design matrix -- the F test of some columns of a logistic regression given the others: covariates, pairs, slopes --, on the same handle: one more call, likewise */
+#include "mdk_mdiff.h"
 void md_stats_close(md_stats *h);
 const char *md_stats_last_error(void);
 

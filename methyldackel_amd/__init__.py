@@ -2526,6 +2526,21 @@ class Cohort:
         cols.update(zip((name for name, _ in GROUP_RESULT_COLUMNS), out[2:]))
         return GroupDiff(self.contigs, cols, out[0], out[1], merged=self.merged, names=names, _text=self._text)
 
+    def diff_model(self, design, test, samples=None, min_dispersion=1.0, names=None):
+        """The site-by-site test WITH COVARIATES: the table's counts regressed on a design matrix and some of its columns tested given
+        the others by ``diff_model`` -- a paired design (a dummy per patient beside the group), a batch, sex or age beside the variable
+        of interest, the slope of a dose or a time.  ``design`` is ``[S', p]`` (anything that converts to float64 on the host), a row
+        per used sample, ``samples`` the table's sample of every row (default: all of them in order; the others are not read), ``test``
+        a column index or a sequence of them, ``names`` the columns' names for ``write`` (``x0``, ``x1``, ... by default).  A
+        ``ModelDiff`` with this table's site columns (the same tensors), the used samples' pooled counts, the coefficients ``[p, n]``
+        and the test's ``pvalue``, ``df``, ``dispersion``, ``statistic``, ``flags`` and ``iterations``.  Regions are joined on a pair's
+        direction: ``cohort.diff(a, b).dmrs(model.qvalue() < 0.05)``."""
+        out = diff_model(self.nmeth, self.nunmeth, design, test, samples=samples, min_dispersion=min_dispersion)
+        cols = {name: getattr(self, name) for name, _ in DIFF_SITE_COLUMNS}
+        cols.update(zip((name for name, _ in MODEL_RESULT_COLUMNS), out[1:]))
+        tested = _model_arguments("diff_model", self.nmeth, self.nunmeth, design, test, samples)[7]
+        return ModelDiff(self.contigs, cols, out[0], tested, merged=self.merged, names=names)
+
     def moments(self, min_depth=1):
         """How alike the table's samples are, the first look after ``unite`` -- methylKit's ``getCorrelation``: a ``SampleMoments`` of
         the two matrices with the table's ``names``, made on the device by ``sample_moments``, which documents the rule.  A site a
@@ -2921,8 +2936,8 @@ def diff_replicates(nmeth, nunmeth, a, b, min_dispersion=1.0, steps=False):
     (csrc/mdk_qdiff_core.h): the same bits on every run and every device; the p-value's relative error is bounded by (4 steps + 12 nu +
     32) * 2^-53 from 1e-280 up, and it is 0.0 below that.  ``min_dispersion`` is a finite float within [2^-55, 2^800].  A negative
     entry, an entry of 2^26 or more and a pooled margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do CPU
-    tensors: there is no CPU path.  Not here: covariates, one-sided tests, the deviance statistic; more than two groups are
-    ``diff_groups``'."""
+    tensors: there is no CPU path.  Not here: one-sided tests, the deviance statistic; more than two groups are ``diff_groups``',
+    covariates, pairs and trends ``diff_model``'s."""
     import torch
     if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
         raise MdkError(f"diff_replicates: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
@@ -3023,7 +3038,8 @@ def diff_groups(nmeth, nunmeth, groups, min_dispersion=1.0, steps=False):
     bounded by (4 steps + 12 (nu + q) + 32) * 2^-53 from 1e-280 up, and it may be 0.0 below that.  Refusals are ``diff_replicates``':
     a negative entry, an entry of 2^26 or more and a pooled margin -- a group's depth, the methylated or the unmethylated of all
     groups -- of 2^26 or more raise MdkError (rc -3) naming the first such site; so do CPU tensors: there is no CPU path.  Not here:
-    covariates, the deviance statistic, one-sided or trend tests, a chi-square p-value for designs without replicates."""
+    the deviance statistic, one-sided tests, a chi-square p-value for designs without replicates; covariates, pairs and trend tests
+    are ``diff_model``'s."""
     import torch
     if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
         raise MdkError(f"diff_groups: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
@@ -3045,6 +3061,144 @@ def diff_groups(nmeth, nunmeth, groups, min_dispersion=1.0, steps=False):
         _side_call(L, "stats", "gdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, group_end, G,
                    float(min_dispersion), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
     return tuple(out)
+
+
+# ---- a design matrix: covariates, pairs, slopes (include/mdk_mdiff.h, csrc/mdk_mdiff.hip in libmdk_stats.so; the rule is csrc/mdk_mdiff_core.h) ----
+MODEL_RESULT_COLUMNS = (("nmeth", "int64"), ("nunmeth", "int64"), ("pvalue", "float64"), ("df", "int32"), ("dispersion", "float64"), ("statistic", "float64"),
+                        ("flags", "uint8"), ("iterations", "int32"))
+MODEL_MAX_COLUMNS = 8
+MODEL_FLAGS = {"rank": 1, "numeric": 2, "reduced": 4, "full": 8}          # MD_STATS_MDIFF_* of include/mdk_mdiff.h
+
+
+def lib_model():
+    """``lib_stats()``'s library with ``diff_model``'s call bound, at the first call that needs it: the one library and the one handle
+    per device of ``diff_replicates``, ``diff_groups``, ``sample_moments`` and ``count_profile``"""
+    L = lib_stats()
+    if "md_stats_mdiff" not in vars(L):
+        L.md_stats_mdiff.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                     C.c_double] + [C.c_void_p] * 10
+    return L
+
+
+def _model_arguments(what, nmeth, nunmeth, design, test, samples):
+    """what ``diff_model`` asks of its arguments, checked before the library is touched, in ``_diff_arguments``' words: (S, n, the used
+    samples ascending, their design rows as lists with the tested columns last, p, q, the place of every column of the caller's in
+    these rows, the tested columns as the caller named them, the matrices' device)"""
+    import math
+    import torch
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise MdkError(f"{what}: {name} must be a [samples, sites] tensor of int32 or int64")
+    if nmeth.dtype != nunmeth.dtype or nmeth.shape != nunmeth.shape:
+        raise MdkError(f"{what}: nmeth is {nmeth.dtype} {tuple(nmeth.shape)}, nunmeth {nunmeth.dtype} {tuple(nunmeth.shape)}: one dtype and one shape")
+    S, n = int(nmeth.shape[0]), int(nmeth.shape[1])
+    if not 1 <= S <= MAX_SAMPLES:
+        raise MdkError(f"{what} takes 1 to {MAX_SAMPLES} samples, not {S}")
+    if n > 1 << 30:
+        raise MdkError(f"{n} sites: more than 2^30")
+    try:
+        rows = design.detach().to("cpu", torch.float64) if isinstance(design, torch.Tensor) else torch.tensor(design, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise MdkError(f"{what}: design must be a [samples, columns] matrix of numbers: {e}") from None
+    if rows.dim() != 2:
+        raise MdkError(f"{what}: design must be a [samples, columns] matrix, not of the shape {tuple(rows.shape)}")
+    rows = rows.tolist()
+    used, p = len(rows), len(rows[0]) if rows else 0
+    if not 2 <= p <= MODEL_MAX_COLUMNS:
+        raise MdkError(f"{what}: a design of {p} columns: 2 to {MODEL_MAX_COLUMNS}")
+    if samples is None:
+        samples = range(S)
+    elif isinstance(samples, (str, bytes)) or not hasattr(samples, "__iter__"):
+        raise MdkError(f"{what}: samples must be a sequence of sample indices, a row of the design each, not {samples!r}")
+    samples = list(samples)
+    if len(samples) != used:
+        raise MdkError(f"{what}: the design has {used} rows for {len(samples)} samples: a row each")
+    seen = set()
+    for i in samples:
+        if isinstance(i, bool) or not hasattr(i, "__index__") or not 0 <= int(i) < S:
+            raise MdkError(f"{what}: samples names sample {i!r}: the matrices hold samples 0 to {S - 1}")
+        if int(i) in seen:
+            raise MdkError(f"{what}: sample {int(i)} is named twice")
+        seen.add(int(i))
+    samples = [int(i) for i in samples]
+    if isinstance(test, (str, bytes)) or not (hasattr(test, "__iter__") or hasattr(test, "__index__")):
+        raise MdkError(f"{what}: test must be a column index of the design or a sequence of them, not {test!r}")
+    tested = [test] if hasattr(test, "__index__") and not hasattr(test, "__iter__") else list(test)
+    for j in tested:
+        if isinstance(j, bool) or not hasattr(j, "__index__") or not 0 <= int(j) < p:
+            raise MdkError(f"{what}: test names column {j!r}: the design has columns 0 to {p - 1}")
+    tested = [int(j) for j in tested]
+    if len(set(tested)) != len(tested):
+        raise MdkError(f"{what}: test names a column twice: {tested}")
+    q = len(tested)
+    if not 1 <= q < p:
+        raise MdkError(f"{what}: {q} tested columns of {p}: 1 to {p - 1}, a reduced model is left")
+    for k, row in enumerate(rows):
+        for j, v in enumerate(row):
+            if not (math.isfinite(v) and abs(v) <= 2.0 ** 20):
+                raise MdkError(f"{what}: the design's entry in row {k}, column {j} is {v!r}: a finite number of at most 2^20 in magnitude")
+    columns = [j for j in range(p) if j not in tested] + tested          # the reduced columns first, then the tested ones: the rule's order
+    by_sample = sorted(range(used), key=lambda k: samples[k])           # ascending sample index: the rule's visiting order
+    rows = [[rows[k][j] for j in columns] for k in by_sample]
+    place = [columns.index(j) for j in range(p)]
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if not t.is_contiguous():
+            raise MdkError(f"{what}: {name} must be contiguous, sample-major")
+    for name, t in (("nmeth", nmeth), ("nunmeth", nunmeth)):
+        if t.device.type != "cuda":
+            raise MdkError(f"a design is fitted on the device: {name} is a {t.device.type} tensor, and there is no CPU path")
+    dev = nmeth.device
+    if nunmeth.device != dev:
+        raise MdkError(f"{what}: nmeth is on {dev}, nunmeth on {nunmeth.device}")
+    return S, n, [samples[k] for k in by_sample], rows, p, q, place, tuple(tested), dev
+
+
+def diff_model(nmeth, nunmeth, design, test, samples=None, min_dispersion=1.0, steps=False):
+    """A site's counts regressed on a DESIGN MATRIX on the device (csrc/mdk_mdiff.hip), and some of its columns tested given the others:
+    what ``diff_replicates`` and ``diff_groups`` cannot do -- a paired design (a dummy per patient beside the group), a batch, sex, age or
+    a cell-type fraction beside the variable of interest, the slope of a dose or a time (the trend test) --, methylKit's
+    ``calculateDiffMeth(covariates=...)`` with ``overdispersion="MN", test="F"``, the score statistic in the place of the deviance.
+    ``nmeth`` and ``nunmeth`` are ``diff_counts``' matrices, checked as it checks them -- a ``Cohort``'s, or a ``CohortRegions``' --;
+    ``design`` is anything ``[S', p]`` that converts to float64 on the host (lists, an array, a tensor), a row per used sample and 2 to
+    8 columns, an intercept among them if the model is to have one; ``samples`` names the row of the matrices of every design row
+    (default: rows 0 .. S' - 1 are all S samples); rows it does not name are not read.  ``test`` is a column index or a sequence of
+    them: the q tested columns, 1 <= q < p; the others are the reduced model.  Per site a sample with ``nmeth + nunmeth == 0`` is not
+    covered and is left out; with k covered samples nu = k - p.  The model is a binomial GLM with logit link, fitted by Newton's method
+    (at most 40 passes a fit, no sample's linear predictor moved by more than 4 in a pass); the statistic is Rao's score statistic of
+    the reduced model against the full one over q times the dispersion -- Pearson's sum of the FULL fit over nu, and ``min_dispersion``
+    where that is smaller --, and the p-value is P(F(q, nu) > statistic).  On an intercept and group dummies that is ``diff_groups``'
+    test, within the two error bounds.  Returns ``coef`` (float64 ``[p, n]``: the full model's coefficients in the design's column
+    order, on the logit scale), ``nmeth`` and ``nunmeth`` (int64: the used samples' entries added), ``pvalue`` (float64), ``df``
+    (int32: nu, 0 below 1), ``dispersion`` and ``statistic`` (float64), ``flags`` (uint8: the bits of ``MODEL_FLAGS``) and
+    ``iterations`` (int32: the passes of both fits); with ``steps=True`` one more, uint32: the terms the tail's series took.  A site
+    with nothing to test -- nu < 1, nothing or everything methylated -- has pvalue 1.0, dispersion 1.0, statistic 0.0 and coefficients
+    0.0; so has a site whose covered samples leave a column of the design dependent on the others or empty (``flags & 1``, df 0) and
+    one where a fit lost a pivot (``flags & 2``).  A fit that did not converge within its 40 passes is reported all the same, with
+    ``flags & 4`` (the reduced fit) or ``flags & 8`` (the full one): a deep sample without a methylated read that has a column to
+    itself does that.  All of it is IEEE arithmetic in one order (csrc/mdk_mdiff_core.h): the same bits on every run and every device;
+    the error bound is the header's.  Refusals are ``diff_replicates``': a negative entry, an entry of 2^26 or more and a pooled
+    margin of 2^26 or more raise MdkError (rc -3) naming the first such site; so do a design whose columns are dependent over its
+    samples, and CPU tensors: there is no CPU path.  Not here: the deviance statistic, offsets, interactions or a formula parser, a
+    meth_diff column, shrinkage, more than 8 columns."""
+    import torch
+    if isinstance(min_dispersion, bool) or not isinstance(min_dispersion, (int, float)) or not 2.0 ** -55 <= min_dispersion <= 2.0 ** 800:         # (a NaN is in no range)
+        raise MdkError(f"diff_model: min_dispersion must be a finite number within 2^-55 and 2^800, not {min_dispersion!r}")
+    S, n, used, rows, p, q, place, _, dev = _model_arguments("diff_model", nmeth, nunmeth, design, test, samples)
+    order = (C.c_int32 * len(used))(*used)
+    flat = (C.c_double * (len(used) * p))(*[v for row in rows for v in row])
+    L = lib_model()
+    coef = torch.empty((p, n), dtype=torch.float64, device=dev)
+    out = [torch.empty(n, dtype=getattr(torch, dt), device=dev) for _, dt in MODEL_RESULT_COLUMNS]
+    if steps:
+        out.append(torch.empty(n, dtype=torch.uint32, device=dev))
+    torch.cuda.current_stream(dev).synchronize()             # the matrices are complete, and nothing of torch's is queued on memory it hands out next
+    with _side_locks["stats"]:                               # the handle of diff_replicates: its calls come from one thread at a time
+        h = _side_handle(L, "stats", dev.index or 0)
+        _side_call(L, "stats", "mdiff", h, C.c_void_p(nmeth.data_ptr()), C.c_void_p(nunmeth.data_ptr()), nmeth.element_size(), S, n, order, len(used), flat, p, q,
+                   float(min_dispersion), C.c_void_p(coef.data_ptr()), *([C.c_void_p(t.data_ptr()) for t in out] + ([] if steps else [None])))
+    if place != list(range(p)):
+        coef = coef[torch.tensor(place, dtype=torch.int64, device=dev)].contiguous()          # the caller's column order
+    return (coef,) + tuple(out)
 
 
 # ---- the pairwise sample moments (include/mdk_moments.h, csrc/mdk_moments.hip in libmdk_stats.so; the rule is csrc/mdk_moments_core.h) ----
@@ -3924,6 +4078,65 @@ class GroupDiff:
                 cells = ["%s" % r[0]] + ["%d" % v for v in r[1:5]] + ["%d" % v for pair in r[5:5 + G] for v in pair]
                 d, lo, hi, p, df, dfg, phi, stat = r[5 + G:]
                 f.write("\t".join(cells + ["%.17g" % d, "%d" % lo, "%d" % hi, "%.17g" % p, "%d" % df, "%d" % dfg, "%.17g" % phi, "%.17g" % stat]) + "\n")
+        return path
+
+
+class ModelDiff:
+    """What ``Cohort.diff_model`` returns, one entry per site of the cohort, on its device: ``contig``, ``start``, ``end`` (int32),
+    ``context`` (uint8) and ``strand`` (int8) are the cohort's own tensors; ``nmeth`` and ``nunmeth`` (int64) the used samples' pooled
+    counts; ``coef`` (float64 ``[p, n]``) the full model's coefficients on the logit scale, row j the design's column j; ``pvalue``
+    (float64) the quasi-binomial F test's of the tested columns, ``df`` (int32), ``dispersion`` and ``statistic`` (float64), ``flags``
+    (uint8: the bits of ``MODEL_FLAGS``) and ``iterations`` (int32).  ``contigs`` and ``merged`` are the cohort's; ``n_columns`` is p,
+    ``tested`` the tested columns as the call named them and ``names`` the columns' names.  It is not a ``Diff``: a model has no pair
+    of groups to take a direction from -- ``cohort.diff(a, b).dmrs(model.qvalue() < 0.05)`` joins regions on a pair's."""
+    COLUMNS = DIFF_SITE_COLUMNS + MODEL_RESULT_COLUMNS
+
+    def __init__(self, contigs, columns, coef, tested, merged=False, names=None):
+        self.contigs = contigs
+        for name, _ in self.COLUMNS:
+            setattr(self, name, columns[name])
+        self.coef = coef
+        self.merged = bool(merged)
+        p = int(coef.shape[0])
+        self.tested = tuple(int(j) for j in tested)
+        self.names = _cohort_sample_names(names if names is not None else [f"x{j}" for j in range(p)], p)
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    @property
+    def n_columns(self):
+        return int(self.coef.shape[0])
+
+    def qvalue(self):
+        """the p-values adjusted as Benjamini and Hochberg do, over the sites of this table: ``Diff.qvalue``'s rule"""
+        return _benjamini_hochberg(self.pvalue)
+
+    def select(self, index):
+        """a copy with the sites ``column[index]`` (a boolean mask, an index tensor, a slice): of every column, and of the coefficients
+        along their site axis"""
+        cols = {name: getattr(self, name)[index].contiguous() for name, _ in self.COLUMNS}
+        return ModelDiff(self.contigs, cols, self.coef[:, index].contiguous(), self.tested, self.merged, self.names)
+
+    def rows(self):
+        """(chrom, start, end, context, strand, nmeth, nunmeth, the p coefficients as a tuple, pvalue, df, dispersion, statistic, flags,
+        iterations) tuples on the host"""
+        site = [getattr(self, n).cpu().tolist() for n, _ in DIFF_SITE_COLUMNS + MODEL_RESULT_COLUMNS[:2]]
+        result = [getattr(self, n).cpu().tolist() for n, _ in MODEL_RESULT_COLUMNS[2:]]
+        coef = self.coef.t().cpu().tolist()
+        return [(self.contigs[s[0]],) + s[1:] + (tuple(c),) + r for s, c, r in zip(zip(*site), coef, zip(*result))]
+
+    def write(self, path):
+        """a header line -- ``#chrom start end context strand nmeth nunmeth``, then ``coef.NAME`` for every column of the design, then the
+        six result columns' names --, then a line per site, tab-separated, the contig by its name; formatted on the host, the doubles
+        with %.17g, which reads back to the same bits.  Returns the path."""
+        head = ["#chrom", "start", "end", "context", "strand", "nmeth", "nunmeth"] + [f"coef.{v}" for v in self.names] + [n for n, _ in MODEL_RESULT_COLUMNS[2:]]
+        with open(path, "w") as f:
+            f.write("\t".join(head) + "\n")
+            for r in self.rows():
+                p, df, phi, stat, flags, its = r[8:]
+                f.write("\t".join(["%s" % r[0]] + ["%d" % v for v in r[1:7]] + ["%.17g" % v for v in r[7]] +
+                                  ["%.17g" % p, "%d" % df, "%.17g" % phi, "%.17g" % stat, "%d" % flags, "%d" % its]) + "\n")
         return path
 
 

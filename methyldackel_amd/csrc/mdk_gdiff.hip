@@ -1,5 +1,5 @@
-// mdk_gdiff.hip -- more of libmdk_stats.so (include/mdk_gdiff.h), the last of mdk_qdiff.hip's chain of includes (mdk_profile.hip, the
-// file that ends mdk_qdiff.hip, includes it at its own end): three or more groups of replicate
+// mdk_gdiff.hip -- more of libmdk_stats.so (include/mdk_gdiff.h), in mdk_qdiff.hip's chain of includes (mdk_profile.hip, the
+// file that ends mdk_qdiff.hip, includes it at its own end, and it includes mdk_mdiff.hip at its own): three or more groups of replicate
 // samples compared site by site on the device, the quasi-binomial F test with q = groups - 1 numerator degrees of freedom.  The rule is
 // mdk_gdiff_core.h's; entries, limits and refusals are mdk_diff_core.h's.  The code object, the md_stats handle, its stream, its status
 // word and its error text are mdk_qdiff.hip's.
@@ -168,3 +168,6 @@ extern "C" int md_stats_gdiff(md_stats *h, const void *nmeth, const void *nunmet
              (long long)(first >> 8));
     return MD_STATS_ERR_ARG;
 }
+
+// a design's tested columns given the others -- covariates --: the library's last call, on the same handle
+#include "mdk_mdiff.hip"

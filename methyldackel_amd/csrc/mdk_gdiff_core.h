@@ -7,8 +7,8 @@
 // fraction" -- Pearson's chi-square of the pooled G x 2 table -- over q times the dispersion of McCullagh and Nelder, estimated from
 // Pearson's residuals of the samples around their group's pooled fraction: methylKit's calculateDiffMeth for several treatment levels
 // with overdispersion = "MN", test = "F", the score statistic in the place of the deviance.  With two covered groups every number is
-// mdk_qdiff_core.h's, to the bit.  Not here: covariates, the deviance statistic, one-sided or trend tests, a chi-square p-value for
-// designs without replicates (it needs exp: such a site has p 1.0 and df 0), shrinkage.
+// mdk_qdiff_core.h's, to the bit.  Not here: the deviance statistic, one-sided tests, a chi-square p-value for designs without
+// replicates (such a site has p 1.0 and df 0), shrinkage; covariates, pairs and trend tests are mdk_mdiff_core.h's.
 //
 // The entries and their refusals are mdk_diff_core.h's (diff_entry_check).  Per site the groups are visited in the order given and a
 // group's samples in ascending index, every entry checked first:

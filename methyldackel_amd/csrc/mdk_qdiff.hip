@@ -91,6 +91,7 @@ extern "C" const char *md_stats_last_error(void) { return g_err; }
 
 struct md_stats : SideHandle<StatsStatus, StatsPinned> {
     int32_t *d_order = nullptr, *d_group_end = nullptr;                      // (d_group_end: md_stats_gdiff's, the groups' ends in d_order)
+    SideBuf<double> d_design; SideBuf<double, true> pin_design;            // (md_stats_mdiff's, made at its first call: a row of the design per entry of d_order, and its pinned mirror)
     int32_t mom_shape = 0, mom_chunk = 0, mom_tile = 0, mom_grid = 0;      // md_stats_moments_limits; 0: the default of each
     int32_t prof_range = 0, prof_band = 0, prof_grid = 0;                  // md_stats_profile_limits; likewise
 };
@@ -104,7 +105,7 @@ extern "C" int md_stats_open(int device, md_stats **out) {
 
 extern "C" void md_stats_close(md_stats *h) {
     if(!h) return;
-    h->close(); (void)hipFree(h->d_order); (void)hipFree(h->d_group_end);
+    h->close(); (void)hipFree(h->d_order); (void)hipFree(h->d_group_end); h->d_design.release(); h->pin_design.release();
     delete h;
 }
 

@@ -6,7 +6,7 @@
 // McCullagh and Nelder do, from Pearson's residuals of the samples around their group's pooled fraction: the idea of methylKit's
 // overdispersion = "MN", test = "F", with the score statistic in the place of the deviance.  Fisher's test of the pooled table
 // (mdk_diff_core.h) takes the reads of a group for independent draws; replicates differ by more than that, and this test divides the
-// pooled statistic by how much they do.  Not here: covariates, one-sided tests, the deviance statistic, shrinkage (more groups: mdk_gdiff_core.h).
+// pooled statistic by how much they do.  Not here: one-sided tests, the deviance statistic, shrinkage (more groups: mdk_gdiff_core.h; covariates: mdk_mdiff_core.h).
 //
 // The entries, limits and refusals are mdk_diff_core.h's (diff_entry_check, diff_margin_check; meth_diff is diff_meth).  Per site the
 // samples are visited in ascending index, every entry checked first:
